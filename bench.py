@@ -9,9 +9,18 @@ a row-range shard of a global table (weak scaling) and the per-GPU selected
 counts are exchanged with one RCCL all_gather per step -- the only collective
 the path needs; results stay sharded.
 
-Prints ONE JSON line (rank 0): metric/value (rows/s, whole job), the HBM
-roofline of the fused kernel (HIP events on the launch stream), and the CPU
-oracle timed on a bounded sample on this host.
+Prints ONE JSON line (rank 0): metric/value (rows/s, whole job), ms_per_step
+and the HBM roofline of the fused kernel (HIP events on the launch stream of
+the timed steps themselves). A plain run does only that: set-up, --warmup
+untimed and --steps timed steps, the --dump-outputs files if asked for, the
+line. With --full the line also carries what takes runs of its own: the
+selectivity sweep, the result gather, the parity gates against the CPU oracle,
+the --extra config lines and the CPU oracle timed on a bounded sample on this
+host.
+
+--dump-outputs DIR writes what the last timed step returned to its caller (the
+selected rows of a, b, a*b+c) as DIR/<name>.npy: the inputs are seeded, so two
+builds run with the same arguments can be compared file for file.
 """
 import argparse
 import ctypes as C
@@ -826,8 +835,8 @@ def c2_i64_line(eng, dev, rank, world, steps, warmup, dist, rows, sel=0.5):
     el, kms, selected = timed_steps(step, steps, warmup, dist, eng, dev)
     kname = kernel_name(eng)
     del outs, step
-    gate = prefix_gate(eng, schema, [Array(DataType.Int64, n, c.view(torch.uint8)) for c in cols], 1 << 22, pred,
-                       projs, flags)
+    gate = prefix_gate(eng, schema, [Array(DataType.Int64, n, c.view(torch.uint8)) for c in cols], min(n, 1 << 22),
+                       pred, projs, flags)
     s = selected / n
     bpr = 24.0 + 24.0 * s  # as C2: a, b, c read; s * (a, b, a*b+c) written
     moved = moved_bytes(n, 16, 1, (cols[0] > k) & (cols[1] < m), 24 * selected)
@@ -1350,6 +1359,32 @@ def csv_line(eng, steps, warmup):
     return out
 
 
+DUMP_ROWS = 1 << 20  # rows per dumped column: 4 files of 8 MiB + the counts
+
+
+def dump_outputs(path, outs, selected, n, rank, world):
+    """--dump-outputs: what the last timed step handed to its caller -- the
+    first `selected` rows of the output columns a, b, a*b+c -- as
+    <path>/<name>.npy (float64). Outputs of more than DUMP_ROWS rows are
+    sampled at DUMP_ROWS fixed positions (seeded, sorted; the positions are
+    written too, exact in float64), the same for every column. `counts` holds
+    the input rows and the selected rows. With --gpus N every rank writes its
+    shard's files as <name>.rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    if selected > DUMP_ROWS:
+        g = torch.Generator()
+        g.manual_seed(SEED)
+        idx = torch.randint(0, selected, (DUMP_ROWS,), generator=g).sort().values
+    else:
+        idx = torch.arange(selected)
+    suffix = ".rank%d" % rank if world > 1 else ""
+    didx = idx.to(outs[0].device)
+    for name, t in zip(("a", "b", "a_mul_b_plus_c"), outs):
+        np.save(os.path.join(path, name + suffix + ".npy"), t[:selected][didx].cpu().numpy())
+    np.save(os.path.join(path, "sample_rows" + suffix + ".npy"), idx.numpy().astype(np.float64))
+    np.save(os.path.join(path, "counts" + suffix + ".npy"), np.array([n, selected], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1361,6 +1396,12 @@ def main():
     ap.add_argument("--extra", default="c4,q6,c2i64,c3,groupby,batches",
                     help="extra config lines (comma list: c4,q6,c2i64,c3,groupby,batches,host,csv; empty = none)")
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: --sweep, --gather, the parity gates, the --extra "
+                         "config lines and the CPU baseline (without it those options are not used)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output columns of the last timed step as DIR/<name>.npy (a seeded sample of "
+                         "%d rows per column where there are more)" % DUMP_ROWS)
     ap.add_argument("--exchange", choices=("abi", "torch"), default=None,
                     help="N>1 exchange: the C-ABI RCCL path (dfmi_shard_filter_project, default under nccl) or "
                          "torch.distributed (default for the gloo rehearsal)")
@@ -1401,14 +1442,19 @@ def main():
 
     exchange = args.exchange or ("abi" if BACKEND == "nccl" else "torch")
     comm = None
-    if (world > 1 and exchange == "abi") or (args.gather and (BACKEND == "nccl" or world == 1)):
+    full = args.full
+    if (world > 1 and exchange == "abi") or (full and args.gather and (BACKEND == "nccl" or world == 1)):
         comm = abi_comm(eng, dist, rank, world, dev)
     step_comm = comm if (world > 1 and exchange == "abi") else None
-    sels = [args.sel] + [float(x) for x in args.sweep.split(",") if x and float(x) != args.sel]
+    sels = [args.sel]  # the headline first: its last step's outputs are the ones dumped
+    if full:
+        sels += [float(x) for x in args.sweep.split(",") if x and float(x) != args.sel]
     results = {}
     for sel in sels:
         step = FusedStep(eng, schema, cols, n, *query(sel), outs, comm=step_comm)
         el, kms, selected = timed_steps(step, args.steps, args.warmup, dist, eng, dev, py_exchange=step_comm is None)
+        if args.dump_outputs and sel == args.sel:
+            dump_outputs(args.dump_outputs, outs, selected, n, rank, world)
         s_real = selected / n
         bytes_per_row = 24.0 + 24.0 * s_real  # a,b,c read; s*(a,b,a*b+c) written
         kname = kernel_name(eng)
@@ -1419,13 +1465,15 @@ def main():
     del outs, step
     torch.cuda.empty_cache()
     gather = None
-    if args.gather and comm is not None:
+    if full and args.gather and comm is not None:
         gather = gather_line(eng, comm, schema, cols, n, args.sel, dist, rank, world, dev)
         torch.cuda.empty_cache()
-    from datafusion_amd.arrow import Array
-    gate = prefix_gate(eng, schema, [Array(DataType.Float64, n, c.view(torch.uint8)) for c in cols],
-                       min(n, 1 << 22), *query(args.sel))
-    extras = [x for x in args.extra.split(",") if x]
+    gate = None
+    if full:
+        from datafusion_amd.arrow import Array
+        gate = prefix_gate(eng, schema, [Array(DataType.Float64, n, c.view(torch.uint8)) for c in cols],
+                           min(n, 1 << 22), *query(args.sel))
+    extras = [x for x in args.extra.split(",") if x] if full else []
     extra = {}
     if "batches" in extras:
         extra["batches"] = batches_line(eng, schema, cols, args.sel, dev)
@@ -1478,18 +1526,20 @@ def main():
                                    "row-range shards, %s rehearsal on shared GPUs" % BACKEND) if world > 1
                    else "one GPU"},
         "roofline": h["rl"],
-        "sweep": {("%.2f" % s): {"rows_per_s": n * world * args.steps / r["el"], "kernel_ms": round(r["kms"], 4),
-                                 "hbm_gbs": r["rl"]["achieved"], "frac": r["rl"]["frac"], "selected": r["selected"],
-                                 "roofline": r["rl"]}
-                  for s, r in results.items()},
-        "parity_gate": gate,
+        "full": full,
         "box": {"host": socket.gethostname(), "gpu": _gpu_id(dev)},
     }
+    if full:
+        out["sweep"] = {("%.2f" % s): {"rows_per_s": n * world * args.steps / r["el"], "kernel_ms": round(r["kms"], 4),
+                                       "hbm_gbs": r["rl"]["achieved"], "frac": r["rl"]["frac"],
+                                       "selected": r["selected"], "roofline": r["rl"]}
+                        for s, r in results.items()}
+        out["parity_gate"] = gate
     if gather is not None:
         out["gather"] = gather
     if extra:
         out["extra"] = extra
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         cb = cpu_baseline(args.sel)
         cb["cpu_model"] = _cpu_model()
         cb["nproc"] = os.cpu_count()

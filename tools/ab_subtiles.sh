@@ -14,7 +14,7 @@ mkdir -p $(dirname $OUT)
 for rep in 1 2; do
   for m in $VARIANTS; do
     if [ "$m" = d ]; then E=""; else E="DFMI_DIAG=1 DFMI_NUMERIC_SUBTILES=$m"; fi  # d: the adaptive default
-    env $E timeout -k 10 300 python3 bench.py --steps 10 --warmup 2 --sel 0.01 \
+    env $E timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 2 --sel 0.01 \
         --sweep 0.01 --no-cpu --extra c4 --gather 0 > gpurun_out/ab_sub_$m.json 2> gpurun_out/ab_sub_$m.err \
         || { tail gpurun_out/ab_sub_$m.err; exit 1; }
     python3 - $m $rep >> $OUT <<'EOF'

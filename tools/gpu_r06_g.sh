@@ -11,7 +11,7 @@ if [ $rc -ne 0 ]; then exit $rc; fi
 timeout -k 10 300 python3 -u tools/groupby_probe.py 1e7 --no-host --sweep --phases > $OUT/sweep.log 2>&1 || { cat $OUT/sweep.log; exit 1; }
 cat $OUT/sweep.log
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o gb -- python3 $R/bench.py --steps 3 --warmup 1 --extra groupby > $OUT/bench_gb.json 2> $OUT/bench_gb.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o gb -- python3 $R/bench.py --full --steps 3 --warmup 1 --extra groupby > $OUT/bench_gb.json 2> $OUT/bench_gb.err
 rc=$?
 tail -c 1500 $OUT/bench_gb.err
 exit $rc

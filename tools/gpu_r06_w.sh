@@ -9,4 +9,4 @@ tail -2 $OUT/pytest.log
 if [ $rc -ne 0 ]; then exit $rc; fi
 timeout -k 10 300 python3 -u tools/groupby_probe.py 1e7 --no-host --sweep --phases > $OUT/sweep.log 2>&1 || { cat $OUT/sweep.log; exit 1; }
 grep -v "^/opt" $OUT/sweep.log
-timeout -k 10 400 python3 bench.py --steps 3 --warmup 1 --extra groupby > $OUT/bench_gb.json 2> $OUT/bench_gb.err
+timeout -k 10 400 python3 bench.py --full --steps 3 --warmup 1 --extra groupby > $OUT/bench_gb.json 2> $OUT/bench_gb.err

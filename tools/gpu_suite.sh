@@ -3,10 +3,10 @@
 # usage: tools/gpu_suite.sh [tag]
 set -o pipefail
 TAG=${1:-suite}
-mkdir -p gpurun_out
-timeout -k 10 840 python -u -m pytest tests -m gpu -x -v --durations=30 --timeout 120 --timeout-method thread > gpurun_out/pytest_$TAG.log 2>&1
-rc=$?; tail -5 gpurun_out/pytest_$TAG.log; [ $rc -ne 0 ] && exit $rc
-timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke_$TAG.log 2>&1 || { cat gpurun_out/smoke_$TAG.log; exit 1; }
-cat gpurun_out/smoke_$TAG.log
-timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { tail gpurun_out/bench_$TAG.err; exit 1; }
-cat gpurun_out/bench_$TAG.json
+mkdir -p bench_out
+timeout -k 10 840 python -u -m pytest tests -m gpu -x -v --durations=30 --timeout 120 --timeout-method thread > bench_out/pytest_$TAG.log 2>&1
+rc=$?; tail -5 bench_out/pytest_$TAG.log; [ $rc -ne 0 ] && exit $rc
+timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > bench_out/smoke_$TAG.log 2>&1 || { cat bench_out/smoke_$TAG.log; exit 1; }
+cat bench_out/smoke_$TAG.log
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu > bench_out/bench_$TAG.json 2> bench_out/bench_$TAG.err || { tail bench_out/bench_$TAG.err; exit 1; }
+cat bench_out/bench_$TAG.json

@@ -22,8 +22,8 @@ for run in $RUNS; do
   D=$OUT/$run
   mkdir -p $D
   echo "== $run: $ARGS"
-  eval timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/kt -o kt -- python3 $R/bench.py $ARGS > $D/bench.json 2> $D/kt.err || { tail $D/kt.err; exit 1; }
-  eval timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D/fetch -o fetch -- python3 $R/bench.py $ARGS > $D/fetch_bench.json 2> $D/fetch.err || { tail $D/fetch.err; exit 1; }
-  eval timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/write -o write -- python3 $R/bench.py $ARGS > $D/write_bench.json 2> $D/write.err || { tail $D/write.err; exit 1; }
+  eval timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/kt -o kt -- python3 $R/bench.py --full $ARGS > $D/bench.json 2> $D/kt.err || { tail $D/kt.err; exit 1; }
+  eval timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D/fetch -o fetch -- python3 $R/bench.py --full $ARGS > $D/fetch_bench.json 2> $D/fetch.err || { tail $D/fetch.err; exit 1; }
+  eval timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/write -o write -- python3 $R/bench.py --full $ARGS > $D/write_bench.json 2> $D/write.err || { tail $D/write.err; exit 1; }
   python3 $R/tools/traffic.py $D || exit 1
 done

@@ -11,7 +11,7 @@ ARGS=(${FILES:-tests/test_gpu_batches.py tests/test_gpu_parity.py})
 timeout -k 10 ${PT_TIMEOUT:-600} python -u -m pytest -x -v --timeout 120 --timeout-method thread "${ARGS[@]}" \
     > gpurun_out/pytest_$TAG.log 2>&1
 rc=$?; tail -5 gpurun_out/pytest_$TAG.log; [ $rc -ne 0 ] && exit $rc
-timeout -k 10 400 python -u bench.py --steps 5 --warmup 2 --no-cpu --sweep "" --extra ${EXTRA:-batches,c3} --gather 0 \
+timeout -k 10 400 python -u bench.py --full --steps 5 --warmup 2 --no-cpu --sweep "" --extra ${EXTRA:-batches,c3} --gather 0 \
     > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { tail -30 gpurun_out/bench_$TAG.err; exit 1; }
 python -c "
 import json,sys

@@ -5,7 +5,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 for rep in 1 2; do for t in 0 1; do
-  DFMI_DIAG=1 DFMI_TICKET=$t timeout -k 10 300 python3 bench.py --steps 10 --warmup 2 --sweep 0.5,0.01 --no-cpu \
+  DFMI_DIAG=1 DFMI_TICKET=$t timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 2 --sweep 0.5,0.01 --no-cpu \
       --extra c4,c3 --gather 0 > gpurun_out/tk_$t.json 2> gpurun_out/tk_$t.err || { tail gpurun_out/tk_$t.err; exit 1; }
   python3 - $t $rep <<'PY' | tee -a gpurun_out/ticket_ab.log
 import json, sys

@@ -5,7 +5,7 @@ set -o pipefail
 mkdir -p gpurun_out
 for rep in 1 2; do
   for zc in ${VARIANTS:-0 1}; do
-    DFMI_HOST_ZC=$zc timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu --sweep "" --extra batches \
+    DFMI_HOST_ZC=$zc timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu --sweep "" --extra batches \
         --gather 0 > gpurun_out/zc_$zc.json 2> gpurun_out/zc_$zc.err || { tail -20 gpurun_out/zc_$zc.err; exit 1; }
     python3 - $zc $rep <<'PY' | tee -a gpurun_out/zc_ab.log
 import json, sys
