@@ -1,0 +1,235 @@
+// Aggregate extension: the state behind dfmi_agg_state, the buffers it owns,
+// and what the device hash table's driver (agg_hash.cpp) offers the entry
+// points (aggregate.cpp).
+#pragma once
+#include <cstdlib>
+#include <memory>
+#include <unordered_map>
+#include <vector>
+
+#include "agg_host.h"
+#include "exec_internal.h"
+#include "groupby.h"
+
+namespace dfmi {
+namespace agg {
+
+// Pinned host memory that keeps its capacity (a finish's copies land here by
+// DMA; no zero-fill, no page faults once warm).
+template <typename T>
+struct HostBuf {
+    T* p = nullptr;
+    size_t n = 0, cap = 0;
+    HostBuf() = default;
+    HostBuf(const HostBuf&) = delete;
+    HostBuf& operator=(const HostBuf&) = delete;
+    ~HostBuf() {
+        if (p) (void)hipHostFree(p);
+    }
+    void resize(size_t want) {
+        if (want > cap) {
+            if (p) (void)hipHostFree(p);
+            p = nullptr;
+            cap = 0;
+            const size_t c = std::max<size_t>(want + want / 4, 16);
+            HIP_TRY(hipHostMalloc((void**)&p, c * sizeof(T), hipHostMallocDefault));
+            cap = c;
+        }
+        n = want;
+    }
+    T* data() { return p; }
+    const T* data() const { return p; }
+    size_t size() const { return n; }
+    T& operator[](size_t i) { return p[i]; }
+    const T& operator[](size_t i) const { return p[i]; }
+};
+
+// Device memory with one owner (move-only; freed with it).
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;  // bytes
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    template <typename T>
+    T* as() const { return (T*)p; }
+    // A block of exactly `bytes` (the old one freed first, its contents dropped).
+    void alloc(size_t bytes) {
+        if (p) HIP_TRY(hipFree(p));
+        p = nullptr;
+        cap = 0;
+        HIP_TRY(hipMalloc(&p, bytes));
+        cap = bytes;
+    }
+    // At least `bytes` (64 at the least): a scratch buffer that keeps its
+    // capacity and grows with 25 % slack, contents dropped.
+    void* reserve(size_t bytes) {
+        bytes = std::max<size_t>(bytes, 64);
+        if (cap < bytes) alloc(bytes + bytes / 4);
+        return p;
+    }
+    // A block of `want` bytes with the first `keep` bytes copied over.
+    void regrow(dfmi_context* ctx, size_t keep, size_t want) {
+        DevBuf q;
+        q.alloc(want);
+        if (keep) HIP_TRY(hipMemcpyAsync(q.p, p, keep, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        *this = std::move(q);  // (the old block goes with q)
+    }
+};
+
+// The device hash table of a grouped state (groupby.h; kernels in groupby.hip).
+struct HashDev {
+    // The scratch buffers, one slot per use: no two uses that are live at the
+    // same time share one.
+    enum Slot {
+        EvalOut = 0,  // the evaluation pass: up to three per output column (values or offsets + bytes, validity)
+        DrainNull = EvalOut + 3 * (dfmi::gb::kMaxKeys + dfmi::gb::kMaxAggs),  // read_table / finish_device: the
+        DrainKeyWords, DrainKeyLens,                                          // compacted keys,
+        DrainRounded,                                                         // the records k_group_round finished
+        // accumulate_bucketed: group id per row; per (bucket, block) counts, then starts; bucket totals; the batch
+        // partitioned by bucket: group ids, NULL masks, payload words
+        BucketRowGroup, BucketHist, BucketTotals, BucketPartGroup, BucketPartNull, BucketPartValues,
+        // finish_device: the caller's arrays on the device; the radix sort's double buffers and scratch
+        EmitKeys, EmitValues, EmitSortKeys, EmitSortKeys2, EmitSortVals, EmitSortVals2, EmitNullAt, EmitTemp,
+        kSlots
+    };
+    DevBuf ctl, slot;                 // the table's storage; `t` views it
+    dfmi::gb::Table t{};
+    uint64_t cap = 0;                 // slots
+    DevBuf hdr;                       // dfmi::gb::Hdr: device counters
+    HostBuf<dfmi::gb::Hdr> hh;        // pinned host copy
+    DevBuf arena;                     // Utf8 key bytes
+    uint64_t arena_cap = 0;
+    DevBuf acc;                       // [acc_cap][words] group records
+    uint64_t acc_cap = 0;
+    DevBuf pattern;                   // one zero-state record (device)
+    std::vector<uint64_t> hpattern;
+    int words = 0;
+    std::vector<int> off, foff;       // per aggregate: record offset; float SUMs: digit offsets
+    DevBuf sidx, coll;
+    int64_t rows_cap = 0;             // sidx / coll capacity
+    uint32_t epoch = 0;
+    uint64_t ngroups = 0;             // groups the device holds
+    uint64_t rows_since_norm = 0;     // rows added since the digits were last carry-normalised
+    DevBuf bufs[kSlots];              // scratch (the fused pass's output columns, drains, buckets, emission)
+
+    dfmi::gb::Hdr* dhdr() const { return hdr.as<dfmi::gb::Hdr>(); }
+    unsigned long long* records() const { return acc.as<unsigned long long>(); }
+};
+
+// The device hash table's groups as flat host arrays by group id (read_table;
+// for a finish, `rounded`: the records finished on the device and the table
+// left as it is):
+// keys (null bits, words: the value bits or the Utf8 arena offset, lengths),
+// the records, the Utf8 arena, and `order` -- the group ids in key order.
+struct FlatGroups {
+    bool rounded = false;  // acc: the device finish's compact records (groupby.h RoundArgs), the table kept
+    uint64_t ng = 0;
+    size_t nk = 0;
+    int words = 0;
+    std::vector<int> off;
+    std::vector<uint32_t> order;
+    HostBuf<unsigned> knull, klen;
+    HostBuf<uint64_t> kw, acc;
+    HostBuf<uint8_t> arena;
+};
+
+}  // namespace agg
+}  // namespace dfmi
+
+struct dfmi_agg_state {
+    int device = 0;
+    std::vector<const dfmi_aggregate*> aggs;
+    dfmi::agg::DevBuf acc;  // uint64 [kAggCopies][n][kAggWords]; grouped: [kAggCopies][gslots][n + 1][kAggWords]
+    size_t acc_words = 0;
+    bool failed = false;      // a batch raised an error: the query has failed
+    dfmi_error failure{};
+    std::vector<uint64_t> init;  // the zero state (MIN keys all ones)
+    // GROUP BY extension (dfmi_agg_state_create_grouped / _multi)
+    bool grouped = false;
+    std::vector<dfmi_program> keys;  // the key expressions (copies: same uid, same kernels)
+    dfmi_program key;           // keys[0] (the window kernel's key)
+    int gslots = 0;             // window slots per accumulator copy: the key window + the null slot
+    uint64_t win_base = 0;      // the window the device accumulators hold ...
+    int win_width = -1;         // ... (-1: none yet)
+    bool dirty = false;         // the device window accumulators hold rows
+    dfmi::aggh::GroupMap groups;  // merged groups (window flushes, hash-table drains, host merges)
+    // the host merge's per-row lookup: encoded key -> entry of `groups` (map
+    // nodes do not move), cleared with it
+    std::unordered_map<std::string, std::vector<dfmi::aggh::Partial>*> index;
+    std::shared_ptr<dfmi::aggh::GroupMap> shown;  // groups dfmi_shard_agg_finish_grouped merged (else `groups`)
+    std::unique_ptr<dfmi::agg::HashDev> hd;       // device hash table (created on first use)
+    std::unique_ptr<dfmi::agg::FlatGroups> flat;  // a finish's groups, not yet in `groups` (finish_flat)
+    std::unique_ptr<dfmi::agg::FlatGroups> spare_flat;  // a used one, its pinned buffers kept for the next drain
+    // integer keys: the per-batch key window comes from MIN / MAX of the key
+    // over the batch's selected rows (a pre-pass through this same extension)
+    dfmi_aggregate* mm[2] = {nullptr, nullptr};
+    dfmi_agg_state* mm_state = nullptr;
+};
+
+namespace dfmi {
+namespace agg {
+
+// The diagnostic knobs of the aggregate path (DFMI_DIAG=1 and ...), read once
+// per entry point -- per call, never cached: tests switch them within one
+// process -- and nothing but DFMI_DIAG read when that is unset. A knob that
+// carries a value is its text, null when unset.
+struct AggDiag {
+    bool group_host = false;      // DFMI_GROUP_HOST: every batch merged on the host (A/B of the hash table)
+    bool host_finish = false;     // DFMI_GROUP_HOST_FINISH: no device rounding / emission
+    bool finish_profile = false;  // DFMI_FINISH_PROFILE: timings on stderr
+    const char* buckets = nullptr;          // DFMI_GROUP_BUCKETS=0 / 1
+    const char* device_emit = nullptr;      // DFMI_GROUP_DEVICE_EMIT=0 / 1
+    const char* hash_bits = nullptr;        // DFMI_GROUP_HASH_BITS
+    const char* subtiles = nullptr;         // DFMI_AGG_SUBTILES
+    const char* rows_per_thread = nullptr;  // DFMI_ROWS_PER_THREAD
+    const char* proj_dense = nullptr;       // DFMI_PROJ_DENSE
+};
+
+inline AggDiag agg_diag() {
+    AggDiag d;
+    if (!getenv("DFMI_DIAG")) return d;
+    d.group_host = getenv("DFMI_GROUP_HOST") != nullptr;
+    d.host_finish = getenv("DFMI_GROUP_HOST_FINISH") != nullptr;
+    d.finish_profile = getenv("DFMI_FINISH_PROFILE") != nullptr;
+    d.buckets = getenv("DFMI_GROUP_BUCKETS");
+    d.device_emit = getenv("DFMI_GROUP_DEVICE_EMIT");
+    d.hash_bits = getenv("DFMI_GROUP_HASH_BITS");
+    d.subtiles = getenv("DFMI_AGG_SUBTILES");
+    d.rows_per_thread = getenv("DFMI_ROWS_PER_THREAD");
+    d.proj_dense = getenv("DFMI_PROJ_DENSE");
+    return d;
+}
+
+// The sticky failure of a state: a batch has failed the query.
+inline void check_not_failed(const dfmi_agg_state* st) {
+    if (st->failed) throw Fail{st->failure.code, st->failure.message};
+}
+
+// ---- agg_hash.cpp: the device hash table's driver
+void group_batch_on_host(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* in,
+                         uint32_t flags);
+void group_batch_hashed(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* in,
+                        uint32_t flags, const AggDiag& diag);
+void reset_table(dfmi_context* ctx, HashDev& H);
+void unflatten(dfmi_agg_state* st);
+void drain_hashed(dfmi_context* ctx, dfmi_agg_state* st);
+bool finish_flat(dfmi_context* ctx, dfmi_agg_state* st, const AggDiag& diag);
+bool finish_device(dfmi_context* ctx, dfmi_agg_state* st, const AggDiag& diag, int64_t cap, dfmi_agg_value* keys,
+                   dfmi_agg_value* values, int64_t* num_groups);
+void emit_flat(const dfmi_agg_state* st, const FlatGroups& f, int64_t cap, dfmi_agg_value* keys,
+               dfmi_agg_value* values, int64_t* num_groups);
+void emit_key_bytes_flat(const FlatGroups& f, int part, int32_t* offsets, int64_t num_offsets, uint8_t* data,
+                         int64_t data_capacity, int64_t* data_length);
+long bucketed_batches();
+
+}  // namespace agg
+}  // namespace dfmi

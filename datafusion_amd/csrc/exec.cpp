@@ -35,6 +35,7 @@ hipError_t launch_utf8_copy_rows(const int32_t* offs, const int32_t* spos, const
 using namespace dfmi;
 
 #include "exec_internal.h"
+#include "launch_args.h"
 #include "batch_stage.h"
 #include "slice.h"
 
@@ -408,7 +409,7 @@ extern "C" int32_t dfmi_context_create(int32_t device, void* stream, dfmi_contex
     }
     dfmi_context* c = new (std::nothrow) dfmi_context();
     if (!c) return DFMI_ERR_INVALID_ARGUMENT;
-    try {
+    return guarded(err, [&]() -> int32_t {
         HIP_TRY(hipSetDevice(device));
         c->device = device;
         c->stream = (hipStream_t)stream;
@@ -418,13 +419,11 @@ extern "C" int32_t dfmi_context_create(int32_t device, void* stream, dfmi_contex
         HIP_TRY(hipEventCreate(&c->ev0));
         HIP_TRY(hipEventCreate(&c->ev1));
         HIP_TRY(hipEventCreate(&c->ev2));
-    } catch (const Fail& f) {
-        set_err(err, f.code, f.msg);
+        *out = c;
+        return DFMI_OK;
+    }, [&] {
         delete c;
-        return f.code;
-    }
-    *out = c;
-    return DFMI_OK;
+    });
 }
 
 namespace dfmi {
@@ -510,7 +509,6 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
                                        const dfmi_program* const* projs, int32_t np,
                                        const dfmi_batch* in, dfmi_out_column* outs, uint32_t flags,
                                        dfmi_error* err) {
-    set_err(err, DFMI_OK, "");
     if (ctx) ctx->last_err_key = ~0ull;
     // DFMI_DIAG + DFMI_CALL_PROFILE: per-phase host time of this entry point,
     // averaged over 1000 calls on stderr (diagnostics only)
@@ -522,7 +520,7 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
         return std::chrono::duration<double, std::micro>(b - a).count();
     };
     auto t_a = tnow();
-    try {
+    return guarded(err, [&]() -> int32_t {
         if (!ctx || !in || (np > 0 && !projs) || !outs || (in->num_columns > 0 && !in->columns))
             throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         if (!pred && np == 0) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "neither a predicate nor projections"};
@@ -566,14 +564,7 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
         Args A;
         memset(&A, 0, sizeof A);
         if (launch) {
-            hipFunction_t fn;
-            try {
-                fn = jit::get_kernel(ctx->device, plan, X, &ctx->last_compile_ms);
-                ctx->last_kernel = X.kname;
-            } catch (const Fail& f) {
-                if (se.set) throw Fail{se.code, se.msg};  // the reference fails first
-                throw;
-            }
+            hipFunction_t fn = query_kernel(ctx, plan, X, se);
             auto t_c = tnow();
             if (prof) ph[1] += tms(t_b, t_c);
             const int n_chan = pred ? 1 + (int)X.utf8_outs.size() : 0;
@@ -596,22 +587,7 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
             if (two_pass) ensure(ctx, &ctx->utf8_src, &ctx->utf8_src_bytes, X.utf8_outs.size() * src_bytes);
             A.n_rows = n;
             A.n_tiles = (int)n_tiles;
-            for (size_t s = 0; s < X.num_cols.size(); ++s) {
-                const dfmi_column& c = in->columns[X.num_cols[s]];
-                if (!c.values) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "column values pointer is NULL"};
-                const int w = jit::type_width(c.type);
-                if (w && ((uintptr_t)c.values & (w - 1)))
-                    throw Fail{DFMI_ERR_INVALID_ARGUMENT, "column values must be aligned to their width"};
-                A.col[s] = c.values;
-                A.valid[s] = (c.validity && c.null_count > 0) ? c.validity : nullptr;
-            }
-            for (size_t u = 0; u < X.utf8_cols.size(); ++u) {
-                const dfmi_column& c = in->columns[X.utf8_cols[u]];
-                if (!c.values || !c.offsets) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "Utf8 column buffers are NULL"};
-                A.offs[u] = c.offsets;
-                A.bytes[u] = (const u8*)c.values;
-                A.svalid[u] = (c.validity && c.null_count > 0) ? c.validity : nullptr;
-            }
+            bind_inputs(A, X, in);
             std::vector<uint8_t*> bool_dst(nout, nullptr);
             for (int o = 0; o < nout; ++o) {
                 A.out[o] = outs[o].values;
@@ -629,35 +605,22 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
             }
             for (size_t i = 0; i < valid_out.size(); ++i)
                 A.out_valid[valid_out[i]] = ctx->scratch + (bool_out.size() + i) * row_bytes;
-            memcpy(A.lits, X.args_lits, sizeof A.lits);
-            memcpy(A.str_off, X.str_off, sizeof A.str_off);
-            memcpy(A.str_len, X.str_len, sizeof A.str_len);
-            memcpy(A.str, X.str, sizeof A.str);
+            bind_literals(A, X);
             // A look-back that made no progress for 2 s (ERRK_LOOKBACK_TIMEOUT:
             // e.g. the GPU time-sliced away from this queue for that long) is
             // relaunched once over a freshly zeroed workspace before it is
             // reported as a device error; the relaunch rewrites every output.
             for (int attempt = 0;; ++attempt) {
                 const WsLease ws = ws_acquire(ctx, status_bytes, st);
-                uint8_t* hdr = ws.hdr;
-                A.ticket = (unsigned*)(hdr + kHdrTicket);
-                A.err = (unsigned long long*)(hdr + kHdrErr);
-                A.totals = (unsigned long long*)(hdr + kHdrTotals);
+                bind_workspace(A, ws);
                 A.status = (unsigned long long*)ws.status;
-                A.stats = (unsigned long long*)(hdr + kHdrStats);
-                A.clear_status = (unsigned long long*)ws.clear_status;
-                A.clear_words = ws.clear_words;
-                A.clear_hdr = (unsigned long long*)ws.clear_hdr;
                 if (attempt == 0) {
                     A.mode = 0;
                     if (getenv("DFMI_DIAG"))
                         if (const char* m = getenv("DFMI_DEBUG_MODE")) A.mode = atoi(m);  // diagnostics only
                 }
-                const unsigned grid = (unsigned)n_tiles;  // one block per tile
                 if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev0, st));
-                size_t asz = sizeof A;
-                void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-                HIP_TRY(hipModuleLaunchKernel(fn, grid, 1, 1, X.BLOCK, 1, 1, 0, st, nullptr, cfg));
+                launch_query(fn, (unsigned)n_tiles, X.BLOCK, A, st);  // one block per tile
                 ws_commit(ctx, ws);
                 if (two_pass && !(A.mode & 8))
                     for (size_t j = 0; j < X.utf8_outs.size(); ++j) {
@@ -674,18 +637,14 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
                 if (prof) ph[2] += tms(t_c, t_d);
                 auto t_e = tnow();
                 if (prof) ph[3] += tms(t_d, t_e);
-                HIP_TRY(hipMemcpyAsync(ctx->host_hdr, hdr, kHdrAlloc, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(ctx->host_hdr, ws.hdr, kHdrAlloc, hipMemcpyDeviceToHost, st));
                 if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev2, st));
                 HIP_TRY(hipStreamSynchronize(st));
                 auto t_f = tnow();
                 if (prof) ph[4] += tms(t_e, t_f);
                 uint64_t ew;
                 memcpy(&ew, ctx->host_hdr + kHdrErr, 8);
-                if (ew) {
-                    dev_key = ~ew;
-                    dev_kind = (int)(dev_key & 15);
-                    dev_key &= ~15ull;
-                }
+                decode_err_word(ew, dev_key, dev_kind);
                 if (A.mode & 32) {
                     uint64_t g5[5];
                     memcpy(g5, ctx->host_hdr + kHdrStats + 64, sizeof g5);
@@ -727,10 +686,7 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
                     // waits only on running blocks, whatever else holds the CUs
                     X.ticket = 1;
                     fn = jit::get_kernel(ctx->device, plan, X, &ctx->last_compile_ms);
-                    memcpy(A.lits, X.args_lits, sizeof A.lits);  // (that kernel's literal slots)
-                    memcpy(A.str_off, X.str_off, sizeof A.str_off);
-                    memcpy(A.str_len, X.str_len, sizeof A.str_len);
-                    memcpy(A.str, X.str, sizeof A.str);
+                    bind_literals(A, X);  // (that kernel's literal slots)
                     continue;
                 }
                 break;
@@ -780,10 +736,7 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
         }
         if (!launch) HIP_TRY(hipStreamSynchronize(st));
         return DFMI_OK;
-    } catch (const Fail& f) {
-        set_err(err, f.code, f.msg);
-        return f.code;
-    }
+    });
 }
 
 // ------------------------------------------------------- coalesced batches
@@ -824,12 +777,11 @@ int32_t dfmi::filter_project_batches_staged(dfmi_context* ctx, const dfmi_progra
     // phases: checks + plan, kernel lookup, batch table, enqueue, synchronisation, results
     static thread_local CallProf prof("batches_staged");
     prof.start();
-    set_err(err, DFMI_OK, "");
     int32_t dummy_failed;
     if (!failed) failed = &dummy_failed;
     *failed = -1;
     if (ctx) ctx->last_err_key = ~0ull;
-    try {
+    return guarded(err, [&]() -> int32_t {
         if (!ctx || nb < 0 || (nb > 0 && (!ins || !outs)) || (np > 0 && !projs))
             throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         if (!pred && np == 0) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "neither a predicate nor projections"};
@@ -1020,19 +972,10 @@ int32_t dfmi::filter_project_batches_staged(dfmi_context* ctx, const dfmi_progra
                 A.n_rows = maxn;
                 A.n_tiles = (int)T;
                 A.mode = mode;
-                memcpy(A.lits, X.args_lits, sizeof A.lits);
-                memcpy(A.str_off, X.str_off, sizeof A.str_off);
-                memcpy(A.str_len, X.str_len, sizeof A.str_len);
-                memcpy(A.str, X.str, sizeof A.str);
+                bind_literals(A, X);
                 const WsLease ws = ws_acquire(ctx, status_bytes, st);
-                A.ticket = (unsigned*)(ws.hdr + kHdrTicket);
-                A.err = (unsigned long long*)(ws.hdr + kHdrErr);
-                A.totals = (unsigned long long*)(ws.hdr + kHdrTotals);
+                bind_workspace(A, ws);
                 A.status = (unsigned long long*)ws.status;
-                A.stats = (unsigned long long*)(ws.hdr + kHdrStats);
-                A.clear_status = (unsigned long long*)ws.clear_status;
-                A.clear_words = ws.clear_words;
-                A.clear_hdr = (unsigned long long*)ws.clear_hdr;
                 A.tile_batch = (const int*)(dev_meta + table_bytes);
                 A.batch_ptrs = (void* const*)dev_meta;
                 if (stage) {
@@ -1041,9 +984,7 @@ int32_t dfmi::filter_project_batches_staged(dfmi_context* ctx, const dfmi_progra
                     if (X.hdr_out) A.hdr_out = (unsigned long long*)stage->hdr_out;
                 }
                 if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev0, st));
-                size_t asz = sizeof A;
-                void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-                HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)T, 1, 1, X.BLOCK, 1, 1, 0, st, nullptr, cfg));
+                launch_query(fn, (unsigned)T, X.BLOCK, A, st);
                 ws_commit(ctx, ws);
                 if (stage && stage->cleared) *stage->cleared = true;
                 if (X.hdr_out && stage->hdr_written) *stage->hdr_written = true;
@@ -1116,10 +1057,7 @@ int32_t dfmi::filter_project_batches_staged(dfmi_context* ctx, const dfmi_progra
         prof.mark(5);
         prof.done();
         return DFMI_OK;
-    } catch (const Fail& f) {
-        set_err(err, f.code, f.msg);
-        return f.code;
-    }
+    });
 }
 
 // Internal test hook (not part of the C ABI, not declared in include/):
@@ -1130,8 +1068,7 @@ int32_t dfmi::filter_project_batches_staged(dfmi_context* ctx, const dfmi_progra
 extern "C" int64_t dfmi_internal_jit_check(const dfmi_program* pred, const dfmi_program* const* projs, int32_t np,
                                            const dfmi_batch* in, dfmi_out_column* outs, uint32_t flags,
                                            int32_t compile, char* buf, int64_t cap, dfmi_error* err) {
-    set_err(err, DFMI_OK, "");
-    try {
+    return guarded_size(err, [&]() -> int64_t {
         if (!in || (np > 0 && !projs) || !outs) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         Built B;
         build_plan(pred, projs, np, in, outs, flags & ~0x40000000u, B);
@@ -1140,10 +1077,7 @@ extern "C" int64_t dfmi_internal_jit_check(const dfmi_program* pred, const dfmi_
         if (compile) (void)jit::compile_code(src, nullptr);
         if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", src.c_str());
         return (int64_t)src.size();
-    } catch (const Fail& f) {
-        set_err(err, f.code, f.msg);
-        return -(int64_t)f.code;
-    }
+    });
 }
 
 // ---------------------------------------------------------------- datasource
@@ -1164,8 +1098,7 @@ static uint64_t host_splitmix64(uint64_t x) {
 extern "C" int32_t dfmi_generate_column(dfmi_context* ctx, int32_t kind, uint64_t seed, uint32_t col,
                                         int64_t row0, int64_t n, int64_t lo, int64_t hi, void* out,
                                         dfmi_error* err) {
-    set_err(err, DFMI_OK, "");
-    try {
+    return guarded(err, [&]() -> int32_t {
         if (!ctx || !out || n < 0) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "bad argument"};
         HIP_TRY(hipSetDevice(ctx->device));
         const uint64_t key = host_splitmix64(seed + (uint64_t)col * 0xD1B54A32D192ED03ull);
@@ -1178,8 +1111,5 @@ extern "C" int32_t dfmi_generate_column(dfmi_context* ctx, int32_t kind, uint64_
             throw Fail{DFMI_ERR_INVALID_ARGUMENT, "unknown generator"};
         }
         return DFMI_OK;
-    } catch (const Fail& f) {
-        set_err(err, f.code, f.msg);
-        return f.code;
-    }
+    });
 }

@@ -1,6 +1,6 @@
 // Internals shared by the execution entry points (exec.cpp: filter +
-// project, aggregate.cpp: the aggregate extension): the context, the
-// workspace layout, error plumbing.
+// project, aggregate.cpp and agg_hash.cpp: the aggregate extension): the
+// context, the workspace layout, error plumbing.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -80,13 +80,8 @@ struct dfmi_context {
 namespace dfmi {
 namespace xi {
 
-inline void set_err(dfmi_error* err, int32_t code, const std::string& m) {
-    if (!err) return;
-    err->code = code;
-    snprintf(err->message, sizeof err->message, "%s", m.c_str());
-}
-
-#define HIP_TRY(x)                                                                         \
+// (set_err and the entry points' error frame: abi_guard.h, through jit.h)
+#define HIP_TRY(x)                                                                        \
     do {                                                                                   \
         hipError_t e_ = (x);                                                               \
         if (e_ != hipSuccess) throw Fail{DFMI_ERR_DEVICE, std::string(#x ": ") + hipGetErrorString(e_)}; \

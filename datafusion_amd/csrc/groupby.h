@@ -1,4 +1,4 @@
-// Device GROUP BY by hashing (aggregate.cpp "hashed groups", kernels in
+// Device GROUP BY by hashing (agg_hash.cpp "hashed groups", kernels in
 // groupby.hip): the shapes shared by the host side and the fixed kernels.
 //
 // The key and aggregate arguments of a batch are first evaluated by the fused
@@ -21,7 +21,7 @@
 //                       the representative row persists its key. A row
 //                       whose key differs from the slot's (two keys with one
 //                       63-bit hash) is listed; the host merges those rows
-//                       (exactly, aggregate.cpp).
+//                       (exactly, agg_hash.cpp).
 #ifndef DFMI_GROUPBY_H
 #define DFMI_GROUPBY_H
 
@@ -116,7 +116,7 @@ struct AccArgs {
     int32_t* coll_rows;            // [m] rows whose key differs from the slot's
 };
 
-// Bucketed accumulation (many rows per group: aggregate.cpp use_buckets). The
+// Bucketed accumulation (many rows per group: agg_hash.cpp use_buckets). The
 // accumulate pass's scattered record atomics -- one request per lane, the
 // chip's slowest atomic shape (MI355X_MICROARCH.md "Global float atomics") --
 // replaced by a partition of the rows by group and a per-bucket sum in LDS:
@@ -199,7 +199,7 @@ hipError_t launch_buckets(const RankArgs& r, ScatterArgs s, BucketArgs b, hipStr
 // The finish of every group on the device (k_group_round): per group a
 // compact record [rows, then per aggregate nulls, flags, key, aux] -- the
 // record without its exact-sum digits; a floating-point SUM's key word holds
-// its digits rounded once, half to even (aggregate.cpp round_exact restated:
+// its digits rounded once, half to even (agg_host.cpp round_exact restated:
 // kind 1 to a Float64, kind 2 to a Float32's value as a double), and its
 // flags word kRoundZero when the exact sum is 0.
 struct RoundArgs {
@@ -214,10 +214,10 @@ struct RoundArgs {
 constexpr unsigned long long kRoundZero = 1ull << 32;
 
 // The finish's ordering and emission on the device (one fixed-width key part:
-// aggregate.cpp finish_device): every group's sort value (key_ord restated,
+// agg_hash.cpp finish_device): every group's sort value (key_ord restated,
 // the null group ~0 and moved last afterwards), a radix sort of (value, group
 // id), then one dfmi_agg_value per key and per aggregate in key order, from
-// the compact records of k_group_round -- aggregate.cpp finish_normalized
+// the compact records of k_group_round -- agg_host.cpp finish_normalized
 // restated.
 struct EmitArgs {
     const unsigned long long* rec;   // [ngroups][1 + 4 * naggs] compact records

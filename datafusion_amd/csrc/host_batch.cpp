@@ -45,6 +45,8 @@
 #include "slice.h"
 
 using dfmi::Fail;
+using dfmi::xi::guarded;
+using dfmi::xi::set_err;
 
 #define HIP_TRY(x)                                                                         \
     do {                                                                                   \
@@ -519,12 +521,6 @@ Arena& arena_of(dfmi_context* c) {
     return *(Arena*)slot;
 }
 
-void set_err(dfmi_error* err, int32_t code, const std::string& m) {
-    if (!err) return;
-    err->code = code;
-    snprintf(err->message, sizeof err->message, "%s", m.c_str());
-}
-
 // One device/staging buffer of a chunk: `off` in the slot's region, copied
 // from host `src` (input) or into the result (output).
 struct Buf {
@@ -637,11 +633,19 @@ extern "C" int32_t dfmi_filter_project_host(dfmi_context* ctx, const dfmi_progra
                                             const dfmi_program* const* projs, int32_t np,
                                             const dfmi_batch* in, uint32_t flags,
                                             dfmi_host_result** out, dfmi_error* err) {
-    set_err(err, DFMI_OK, "");
     dfmi_host_result* R = nullptr;
     Arena* Ap = nullptr;
     dfmi_host::PinnedPool::Blk bm_stage;
-    try {
+    const auto abandon = [&] {  // the copies in flight drained, the slots and the half-built result released
+        if (Ap && Ap->h2d) {
+            (void)hipStreamSynchronize(Ap->h2d);
+            (void)hipStreamSynchronize(Ap->d2h);
+            for (int s = 0; s < kSlots; ++s) Ap->slot_used[s] = false;
+            if (bm_stage.p) Ap->results->put(bm_stage);
+        }
+        delete R;
+    };
+    const auto body = [&]() -> int32_t {
         if (!ctx || !in || !out || (np > 0 && !projs) || (in->num_columns > 0 && !in->columns))
             throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         *out = nullptr;
@@ -1142,24 +1146,11 @@ extern "C" int32_t dfmi_filter_project_host(dfmi_context* ctx, const dfmi_progra
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - call_t0).count());
         *out = R;
         return DFMI_OK;
-    } catch (const Fail& f) {
-        if (Ap && Ap->h2d) {
-            (void)hipStreamSynchronize(Ap->h2d);
-            (void)hipStreamSynchronize(Ap->d2h);
-            for (int s = 0; s < kSlots; ++s) Ap->slot_used[s] = false;
-            if (bm_stage.p) Ap->results->put(bm_stage);
-        }
-        delete R;
-        set_err(err, f.code, f.msg);
-        return f.code;
+    };
+    try {
+        return guarded(err, body, abandon);
     } catch (const std::bad_alloc&) {
-        if (Ap && Ap->h2d) {
-            (void)hipStreamSynchronize(Ap->h2d);
-            (void)hipStreamSynchronize(Ap->d2h);
-            for (int s = 0; s < kSlots; ++s) Ap->slot_used[s] = false;
-            if (bm_stage.p) Ap->results->put(bm_stage);
-        }
-        delete R;
+        abandon();
         set_err(err, DFMI_ERR_INVALID_ARGUMENT, "host allocation failed");
         return DFMI_ERR_INVALID_ARGUMENT;
     }
@@ -1471,12 +1462,11 @@ extern "C" int32_t dfmi_filter_project_host_batches(dfmi_context* ctx, const dfm
     // phases: checks + layout, packing into pinned memory, structs, the staged call, result views
     static thread_local dfmi::CallProf prof("host_batches");
     prof.start();
-    set_err(err, DFMI_OK, "");
     int32_t dummy_failed;
     if (!failed) failed = &dummy_failed;
     *failed = -1;
     dfmi_host_result* R = nullptr;
-    try {
+    return guarded(err, [&]() -> int32_t {
         if (!ctx || !out || nb < 0 || (nb > 0 && !ins) || (np > 0 && !projs))
             throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         *out = nullptr;
@@ -1561,19 +1551,16 @@ extern "C" int32_t dfmi_filter_project_host_batches(dfmi_context* ctx, const dfm
         prof.mark(4);
         prof.done();
         return DFMI_OK;
-    } catch (const Fail& f) {
+    }, [&] {
         delete R;
-        set_err(err, f.code, f.msg);
-        return f.code;
-    }
+    });
 }
 
 extern "C" int32_t dfmi_host_batches_output_bytes(const dfmi_program* pred, const dfmi_program* const* projs,
                                                   int32_t np, const dfmi_batch* ins, int32_t nb, uint32_t flags,
                                                   size_t* bytes, dfmi_error* err) {
     (void)flags;
-    set_err(err, DFMI_OK, "");
-    try {
+    return guarded(err, [&]() -> int32_t {
         if (!bytes || nb < 0 || (nb > 0 && !ins) || (np > 0 && !projs))
             throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         *bytes = 0;
@@ -1585,10 +1572,7 @@ extern "C" int32_t dfmi_host_batches_output_bytes(const dfmi_program* pred, cons
         hb_layout(pred, projs, np, ins, nb, Lo);
         *bytes = Lo.OB;
         return DFMI_OK;
-    } catch (const Fail& f) {
-        set_err(err, f.code, f.msg);
-        return f.code;
-    }
+    });
 }
 
 extern "C" int32_t dfmi_filter_project_host_batches_into(dfmi_context* ctx, const dfmi_program* pred,
@@ -1598,13 +1582,12 @@ extern "C" int32_t dfmi_filter_project_host_batches_into(dfmi_context* ctx, cons
                                                          dfmi_out_column* outputs, int32_t* failed, dfmi_error* err) {
     static thread_local dfmi::CallProf prof("host_batches_into");
     prof.start();
-    set_err(err, DFMI_OK, "");
     int32_t dummy_failed;
     if (!failed) failed = &dummy_failed;
     *failed = -1;
     Arena* Ap = nullptr;
     dfmi_host::PinnedPool::Blk stage_blk;
-    try {
+    return guarded(err, [&]() -> int32_t {
         if (!ctx || nb < 0 || (nb > 0 && (!ins || !outputs || !out_block)) || (np > 0 && !projs))
             throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         dfmi::ctx_last_err_key(ctx) = ~0ull;
@@ -1729,9 +1712,7 @@ extern "C" int32_t dfmi_filter_project_host_batches_into(dfmi_context* ctx, cons
         prof.mark(4);
         prof.done();
         return DFMI_OK;
-    } catch (const Fail& f) {
+    }, [&] {
         if (Ap && stage_blk.p) Ap->results->put(stage_blk);
-        set_err(err, f.code, f.msg);
-        return f.code;
-    }
+    });
 }

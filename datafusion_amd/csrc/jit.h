@@ -8,15 +8,10 @@
 #include <vector>
 
 #include "../../include/dfmi.h"
+#include "abi_guard.h"
 #include "dfmi_program.h"
 
 namespace dfmi {
-
-struct Fail {
-    int32_t code;
-    std::string msg;
-};
-
 namespace jit {
 
 // One output column of the pass.

@@ -276,24 +276,19 @@ void agree(dfmi_context* ctx, dfmi_shard_comm* c, int32_t code, const std::strin
 }  // namespace
 
 extern "C" int32_t dfmi_shard_unique_id(uint8_t* id, dfmi_error* err) {
-    set_err(err, DFMI_OK, "");
-    try {
+    return guarded(err, [&]() -> int32_t {
         if (!id) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         ncclUniqueId u;
         NCCL_TRY(ncclGetUniqueId(&u));
         memcpy(id, u.internal, NCCL_UNIQUE_ID_BYTES);
         return DFMI_OK;
-    } catch (const Fail& f) {
-        set_err(err, f.code, f.msg);
-        return f.code;
-    }
+    });
 }
 
 extern "C" int32_t dfmi_shard_comm_init(dfmi_context* ctx, int32_t world, int32_t rank, const uint8_t* id,
                                         dfmi_shard_comm** out, dfmi_error* err) {
-    set_err(err, DFMI_OK, "");
     dfmi_shard_comm* c = nullptr;
-    try {
+    return guarded(err, [&]() -> int32_t {
         if (!ctx || !id || !out || world < 1 || rank < 0 || rank >= world)
             throw Fail{DFMI_ERR_INVALID_ARGUMENT, "bad argument"};
         c = new dfmi_shard_comm();
@@ -309,14 +304,12 @@ extern "C" int32_t dfmi_shard_comm_init(dfmi_context* ctx, int32_t world, int32_
         c->rec.assign((size_t)world * kRec, 0);
         *out = c;
         return DFMI_OK;
-    } catch (const Fail& f) {
+    }, [&] {
         if (c) {
             delete c->tp;
             delete c;
         }
-        set_err(err, f.code, f.msg);
-        return f.code;
-    }
+    });
 }
 
 extern "C" void dfmi_shard_comm_destroy(dfmi_shard_comm* c) {
@@ -330,8 +323,7 @@ extern "C" int32_t dfmi_shard_filter_project(dfmi_context* ctx, dfmi_shard_comm*
                                              const dfmi_program* const* projs, int32_t np, const dfmi_batch* in,
                                              dfmi_out_column* outs, uint32_t flags, dfmi_shard_placement* place,
                                              dfmi_error* err) {
-    set_err(err, DFMI_OK, "");
-    try {
+    return guarded(err, [&]() -> int32_t {
         if (!ctx || !c || !in || !outs || !place) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         const int nout = np > 0 ? np : in->num_columns;
         if (nout > kMaxOut) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "device program limit: too many output columns"};
@@ -375,20 +367,16 @@ extern "C" int32_t dfmi_shard_filter_project(dfmi_context* ctx, dfmi_shard_comm*
         c->nout = nout;
         placement_of(c->rec.data(), c->world, c->rank, nout, kRec, place);
         return DFMI_OK;
-    } catch (const Fail& f) {
-        set_err(err, f.code, f.msg);
-        return f.code;
-    }
+    });
 }
 
 extern "C" int32_t dfmi_shard_gather_to_root(dfmi_context* ctx, dfmi_shard_comm* c, const dfmi_out_column* local,
                                              const dfmi_out_column* root_outs, int32_t root, dfmi_error* err) {
-    set_err(err, DFMI_OK, "");
     if (!ctx || !c) {
         set_err(err, DFMI_ERR_INVALID_ARGUMENT, "bad argument");
         return DFMI_ERR_INVALID_ARGUMENT;
     }
-    try {
+    return guarded(err, [&]() -> int32_t {
         HIP_TRY(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
         const int nout = c->nout, world = c->world;
@@ -534,19 +522,16 @@ extern "C" int32_t dfmi_shard_gather_to_root(dfmi_context* ctx, dfmi_shard_comm*
             HIP_TRY(hipStreamSynchronize(st));
         }
         return DFMI_OK;
-    } catch (const Fail& f) {
+    }, [&] {
         (void)hipStreamSynchronize(ctx->stream);
-        set_err(err, f.code, f.msg);
-        return f.code;
-    }
+    });
 }
 
 extern "C" int32_t dfmi_shard_agg_finish_grouped(dfmi_context* ctx, dfmi_shard_comm* c, dfmi_agg_state* state,
                                                  const dfmi_aggregate* const* aggs, int32_t n, int64_t cap,
                                                  dfmi_agg_value* keys, dfmi_agg_value* values, int64_t* num_groups,
                                                  dfmi_error* err) {
-    set_err(err, DFMI_OK, "");
-    try {
+    return guarded(err, [&]() -> int32_t {
         if (!ctx || !c || !state || !aggs || !num_groups) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         // round 1: [status | bytes | message] of every rank (a failed state
         // still takes part; every rank reports the first failing rank's error)
@@ -583,17 +568,13 @@ extern "C" int32_t dfmi_shard_agg_finish_grouped(dfmi_context* ctx, dfmi_shard_c
         (void)aggs;  // the state's own aggregates (the binding passes the same ones)
         return dfmi_agg_state_show_merged(state, parts.data(), sizes.data(), c->world, cap, keys, values, num_groups,
                                           err);
-    } catch (const Fail& f) {
-        set_err(err, f.code, f.msg);
-        return f.code;
-    }
+    });
 }
 
 extern "C" int32_t dfmi_shard_agg_finish(dfmi_context* ctx, dfmi_shard_comm* c, dfmi_agg_state* state,
                                          const dfmi_aggregate* const* aggs, int32_t n, dfmi_agg_value* out,
                                          dfmi_error* err) {
-    set_err(err, DFMI_OK, "");
-    try {
+    return guarded(err, [&]() -> int32_t {
         if (!ctx || !c || !state || !aggs || !out) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         const int64_t nb = dfmi_agg_partial_bytes(state);
         // [status | message | partial]: a failed state still takes part (all
@@ -617,10 +598,7 @@ extern "C" int32_t dfmi_shard_agg_finish(dfmi_context* ctx, dfmi_shard_comm* c, 
         std::vector<const void*> parts(c->world);
         for (int r = 0; r < c->world; ++r) parts[r] = &all[(size_t)r * rec + 8 + kMsg];
         return dfmi_agg_merge_partials(aggs, n, parts.data(), c->world, out, err);
-    } catch (const Fail& f) {
-        set_err(err, f.code, f.msg);
-        return f.code;
-    }
+    });
 }
 
 // ------------------------------------------------------------ test hooks

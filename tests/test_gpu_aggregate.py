@@ -341,7 +341,7 @@ def test_group_by_random_keys():
 
 def test_group_by_errors():
     """A batch whose selected keys span more than the device's 16-value window
-    is merged on the host (aggregate.cpp group_batch_on_host) with the
+    is merged on the host (agg_hash.cpp group_batch_on_host) with the
     kernel's rules: the oracle's groups; an error in the key expression is
     raised by both, before any aggregate's, in the reference's evaluation
     order -- in the window path and in the wide one."""

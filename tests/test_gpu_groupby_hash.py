@@ -1,4 +1,4 @@
-"""GPU parity of the device GROUP BY hash table (aggregate.cpp "hashed
+"""GPU parity of the device GROUP BY hash table (agg_hash.cpp "hashed
 groups", groupby.hip): several GROUP BY expressions (sqlplanner.rs:97-117
 plans group_expr as a Vec<Expr>), the table grown past its first size, keys
 forced onto shared hashes (the host merge of colliding rows), the host-merge
@@ -225,7 +225,7 @@ def test_grouped_partials_utf8_and_multi_key_merge():
 
 @pytest.mark.parametrize("buckets", ["0", "1"])
 def test_finish_then_more_rows_partial_and_reset(monkeypatch, buckets):
-    """The finish's flat groups (aggregate.cpp finish_flat: finished on the
+    """The finish's flat groups (agg_hash.cpp finish_flat: finished on the
     device, the table kept): a second finish gives the same groups; rows
     added after a finish merge with the finished groups; the grouped partial
     after a finish holds every group; reset empties -- with the atomic
@@ -433,7 +433,7 @@ def test_group_by_every_argument_type(monkeypatch, buckets):
 
 @pytest.mark.parametrize("kt", ["int64", "uint64", "float64", "float32", "int8", "boolean"])
 def test_group_by_device_emission(monkeypatch, kt):
-    """The finish ordered and emitted on the device (aggregate.cpp
+    """The finish ordered and emitted on the device (agg_hash.cpp
     finish_device: sort values, rocPRIM radix sort, the null group moved
     last, dfmi_agg_value records built on the device), forced on small
     tables (DFMI_GROUP_DEVICE_EMIT=1): keys at their type's extremes next to

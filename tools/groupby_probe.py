@@ -3,7 +3,7 @@
 SUM / COUNT of a Float64 column grouped by a key column -- Int64 keys in a
 16-value window (the fused grouped kernel), Int64 keys over 10,000 values,
 Float64 keys (10,000 values), Utf8 keys (1,000 words and 10,000 words), two
-keys Int64 x Utf8 (the device hash table: aggregate.cpp group_batch_hashed)
+keys Int64 x Utf8 (the device hash table: agg_hash.cpp group_batch_hashed)
 -- each timed end to end (state creation excluded, finish included) after a
 warm-up, and the host-merge A/B (DFMI_DIAG=1 DFMI_GROUP_HOST=1) on the same
 batches; --sweep: Float64 keys of 4 ... 1e6 distinct values instead.
