@@ -32,6 +32,7 @@ DFMI_FLAG_EXT_UTF8_COMPARE = 0x2
 DFMI_FLAG_EXT_CAST = 0x4
 DFMI_FLAG_EXT_IS_NULL = 0x8
 DFMI_FLAG_EXT_AGGREGATE = 0x10
+DFMI_FLAG_EXT_SORT = 0x20
 
 # dfmi_agg_fn (AggregateType, expression.rs:33-40)
 DFMI_AGG_MIN = 0
@@ -129,7 +130,7 @@ class dfmi_agg_value(C.Structure):
 
 
 # include/dfmi.h's DFMI_ABI_VERSION: lib() refuses a library built from another header
-DFMI_ABI_VERSION = 3
+DFMI_ABI_VERSION = 4
 
 # Every symbol include/dfmi.h declares (checked by the CPU test suite).
 EXPORTED = [
@@ -191,6 +192,7 @@ EXPORTED = [
     "dfmi_shard_agg_finish",
     "dfmi_shard_agg_finish_grouped",
     "dfmi_agg_state_free",
+    "dfmi_sort_batches",
     "dfmi_generate_column",  # include/dfmi_datasource.h
     "dfmi_csv_open",
     "dfmi_csv_next",
@@ -410,5 +412,8 @@ def lib() -> C.CDLL:
     L.dfmi_agg_merge_grouped_partials.restype = C.c_int32
     L.dfmi_agg_state_free.argtypes = [C.c_void_p]
     L.dfmi_agg_state_free.restype = None
+    L.dfmi_sort_batches.argtypes = [C.c_void_p, P(dfmi_batch), C.c_int32, P(C.c_int32), P(C.c_int32), C.c_int32,
+                                    C.c_int64, P(dfmi_out_column), C.c_uint32, P(dfmi_error)]
+    L.dfmi_sort_batches.restype = C.c_int32
     _LIB = L
     return L

@@ -432,12 +432,14 @@ hipStream_t ctx_stream(const dfmi_context* c) { return c->stream; }
 void*& ctx_host_arena(dfmi_context* c) { return c->host_arena; }
 uint64_t& ctx_last_err_key(dfmi_context* c) { return c->last_err_key; }
 void host_arena_release(dfmi_context* c);
+void sort_scratch_release(dfmi_context* c);
 }  // namespace dfmi
 
 extern "C" void dfmi_context_destroy(dfmi_context* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     dfmi::host_arena_release(c);
+    dfmi::sort_scratch_release(c);
     if (c->ws) (void)hipFree(c->ws);
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->utf8_src) (void)hipFree(c->utf8_src);

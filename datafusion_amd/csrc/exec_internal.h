@@ -48,6 +48,7 @@ struct dfmi_context {
     // ticket order from the first launch instead of after a 2 s timeout
     bool shared = false;
     void* host_arena = nullptr;  // host_batch.cpp's staging arena (per context: no shared state)
+    void* sort_scratch = nullptr;  // sort.cpp's device scratch, kept across dfmi_sort_batches calls
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     double last_total_ms = 0, last_main_ms = 0, last_compile_ms = 0;
     bool timed = false;

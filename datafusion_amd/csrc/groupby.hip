@@ -13,6 +13,7 @@
 
 #include "../../include/dfmi.h"
 #include "groupby.h"
+#include "sort_key.h"
 #include "jit_skeleton.hip"
 
 namespace dfmi {
@@ -1070,18 +1071,7 @@ __global__ __launch_bounds__(kRoundBlock) void k_group_round(const RoundArgs A) 
 }
 
 // ------------------------------------------------------- device emission
-__device__ __forceinline__ u64 sort_value(int t, u64 bits) {  // key_ord as an unsigned 64-bit order
-    switch (t) {
-        case 11: return (bits >> 63) ? ~bits : (bits | (1ull << 63));  // Float64: totalOrder
-        case 10: {
-            const unsigned b = (unsigned)bits;
-            return (u64)((b >> 31) ? ~b : (b | 0x80000000u));
-        }
-        case 2: case 3: case 4: case 5: return bits ^ (1ull << 63);  // signed: sign-extended bits
-        default: return bits;  // unsigned, Boolean
-    }
-}
-
+// (sort_value, the key order as an unsigned 64-bit order: sort_key.h)
 __global__ __launch_bounds__(256) void k_group_sortkey(int kt, u64 ng, const unsigned* knull, const u64* kw, u64* sk,
                                                        unsigned* sv, unsigned* null_at) {
     for (u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x; g < ng; g += (u64)gridDim.x * blockDim.x) {

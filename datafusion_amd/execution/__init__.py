@@ -6,3 +6,4 @@ from .expression import RuntimeExpr, compile_expr, compile_scalar_expr
 from .filter import FilterRelation
 from .projection import ProjectRelation
 from .relation import DataSourceRelation, Relation
+from .sort import LimitRelation, SortRelation

@@ -90,8 +90,8 @@ class Aggregate(_Plan):
 
 
 class Sort(_Plan):
-    """LogicalPlan::Sort { expr, input, schema } (logicalplan.rs:331-335): planned, not executable
-    (context.rs:161 unimplemented!())."""
+    """LogicalPlan::Sort { expr, input, schema } (logicalplan.rs:331-335): planned; executable only
+    under DFMI_FLAG_EXT_SORT (context.rs:161 unimplemented!())."""
 
     def __init__(self, expr, input, schema: Schema = None):
         self.expr = list(expr)
@@ -103,7 +103,8 @@ class Sort(_Plan):
 
 
 class Limit(_Plan):
-    """LogicalPlan::Limit { limit, input, schema } (logicalplan.rs:310-314): planned, not executable."""
+    """LogicalPlan::Limit { limit, input, schema } (logicalplan.rs:310-314): planned; executable only
+    under DFMI_FLAG_EXT_SORT."""
 
     def __init__(self, limit: int, input, schema: Schema = None):
         self.limit = int(limit)
@@ -178,7 +179,26 @@ class ExecutionContext:
             return ProjectRelation(input_rel, compiled, project_schema, self.device, self.flags, self.coalesce)
         if isinstance(plan, Aggregate):
             return self._execute_aggregate(plan)
+        from .. import _abi
+        if isinstance(plan, (Sort, Limit)) and (self.flags & _abi.DFMI_FLAG_EXT_SORT):
+            return self._execute_sort_limit(plan)
         raise ExecutionError("NotImplemented", "unimplemented!() plan %r" % type(plan).__name__)
+
+    def _execute_sort_limit(self, plan) -> Relation:
+        """The Sort and Limit arms the reference lacks (context.rs:161
+        unimplemented!()), under DFMI_FLAG_EXT_SORT: keys resolved against the
+        Sort's input schema, Limit(Sort(x)) as one SortRelation with the limit."""
+        from .sort import LimitRelation, SortRelation
+        limit = None
+        if isinstance(plan, Limit):
+            limit = plan.limit
+            if not isinstance(plan.input, Sort):
+                return LimitRelation(self.execute(plan.input), limit)
+            plan = plan.input
+        if len(plan.expr) > 8:
+            raise ExecutionError("NotImplemented", "device program limit: more than 8 ORDER BY expressions")
+        input_rel = self.execute(plan.input)
+        return SortRelation(input_rel, plan.expr, input_rel.schema(), self.device, self.flags, limit, self)
 
     def _execute_aggregate(self, plan: "Aggregate") -> Relation:
         """The Aggregate arm the reference lacks (context.rs:161 unimplemented!()),

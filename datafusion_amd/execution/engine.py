@@ -404,6 +404,56 @@ class DeviceEngine:
             return [HostResultBatch.make(schema, block, b, nout) for b in range(done)], error
         return [HostBatchColumns(block, b, nout) for b in range(done)], error
 
+    # ---- sort / limit extension (DFMI_FLAG_EXT_SORT)
+    def sort_batches(self, batches: Sequence[RecordBatch], key_columns: Sequence[int], key_asc: Sequence[bool],
+                     limit: Optional[int] = None, flags: int = 0) -> List[Array]:
+        """Every row of `batches` (one schema; moved to the GPU where they are
+        not there yet, never concatenated) in the stable order of the key
+        columns, or its first `limit` rows: dfmi_sort_batches. Returns one
+        Array per input column."""
+        self.drain()
+        L = _abi.lib()
+        batches = [self.to_device(b) for b in batches]
+        nb = len(batches)
+        if nb == 0:
+            raise ValueError("sort_batches needs at least one batch")
+        keep = [self._batch_struct(b) for b in batches]
+        cb = (_abi.dfmi_batch * nb)(*[k[0] for k in keep])
+        first = batches[0].columns
+        n = sum(b.num_rows() for b in batches)
+        outs_list, keeps = [], []
+        for j, a in enumerate(first):
+            cap = 0
+            if a.data_type == DataType.Utf8:
+                for b in batches:  # the bytes its offsets reference (two words read, not the array)
+                    c = b.columns[j]
+                    if c.length:
+                        ends = c.offsets[[c.offset, c.offset + c.length]].tolist()
+                        cap += ends[1] - ends[0]
+            oc, k = self._alloc_out(a.data_type, n, True, cap)
+            outs_list.append(oc)
+            keeps.append(k)
+        outs = (_abi.dfmi_out_column * max(1, len(first)))(*outs_list)
+        nk = len(key_columns)
+        kc = (C.c_int32 * max(1, nk))(*[int(k) for k in key_columns])
+        ka = (C.c_int32 * max(1, nk))(*[1 if a else 0 for a in key_asc])
+        err = _abi.dfmi_error()
+        L.dfmi_context_set_stream(self.ctx, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        rc = L.dfmi_sort_batches(self.ctx, cb, nb, kc, ka, nk, -1 if limit is None else int(limit), outs, flags,
+                                 C.byref(err))
+        if rc != _abi.DFMI_OK:
+            raise ExecutionError.from_status(rc, err.message.decode("utf-8", errors="replace"))
+        result = []
+        for j, a in enumerate(first):
+            oc, k, t = outs[j], keeps[j], a.data_type
+            nulls = oc.null_count
+            valid = k["validity"] if nulls else None
+            if t == DataType.Utf8:
+                result.append(Array(t, oc.length, k["data"], valid, k["offsets"], nulls))
+            else:
+                result.append(Array(t, oc.length, k["values"], valid, None, nulls))
+        return result
+
     # ---- aggregate extension (DFMI_FLAG_EXT_AGGREGATE)
     def _batch_struct(self, batch: RecordBatch):
         cols = batch.columns

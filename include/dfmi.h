@@ -29,9 +29,10 @@ extern "C" {
 
 /* Version of this header's structs and entry points. 2: dfmi_column.offset
  * (arrow ArrayData::offset), dfmi_abi_version(), the caller-owned output form
- * dfmi_filter_project_host_batches_into. A binding compares the library's
+ * dfmi_filter_project_host_batches_into. 4: dfmi_sort_batches
+ * (DFMI_FLAG_EXT_SORT). A binding compares the library's
  * dfmi_abi_version() with the constant it was built against. */
-#define DFMI_ABI_VERSION 3
+#define DFMI_ABI_VERSION 4
 
 /* DFMI_ABI_VERSION of the loaded library. */
 int32_t dfmi_abi_version(void);
@@ -187,6 +188,13 @@ typedef struct dfmi_expr_node {
                                            executor's unimplemented!() (context.rs:161):
                                            MIN / MAX / SUM / COUNT over the selected
                                            rows, semantics in DESIGN.md §2 */
+
+#define DFMI_FLAG_EXT_SORT         0x20u /* LogicalPlan::Sort and LogicalPlan::Limit
+                                           (sqlplanner.rs:119-163) instead of the executor's
+                                           unimplemented!() (context.rs:161): a stable sort
+                                           of every input row by the key list and / or the
+                                           first n rows, dfmi_sort_batches below, semantics
+                                           in DESIGN.md §2 */
 
 /* Opaque compiled expression: the RuntimeExpr::Compiled of expression.rs:43-50. */
 typedef struct dfmi_program dfmi_program;
@@ -541,6 +549,40 @@ int32_t dfmi_agg_merge_grouped_partials_keys_utf8(const dfmi_aggregate* const* a
 /* Back to the empty state (asynchronous on the context stream): re-running the query. */
 int32_t dfmi_agg_state_reset(dfmi_context* ctx, dfmi_agg_state* state, dfmi_error* err);
 void dfmi_agg_state_free(dfmi_agg_state* state);
+
+/* ---------------------------------------------------------------------------
+ * Sort / Limit extension (DFMI_FLAG_EXT_SORT). The reference plans
+ * `SELECT ... ORDER BY e [ASC|DESC], ... LIMIT n` as Limit(Sort(Projection))
+ * (sqlplanner.rs:119-163) and its executor stops at `unimplemented!()`
+ * (context.rs:161). Build-defined semantics:
+ *   order: lexicographic over the key list, each key in the GROUP BY key order
+ *     above -- false < true, integers numerically, Float32 / Float64 by IEEE
+ *     754 totalOrder with one position per bit pattern, Utf8 bytewise (a
+ *     prefix first) -- and a null greater than every value; a descending key
+ *     reverses its whole comparison (its nulls first); rows equal on every
+ *     key keep their input order (batch order, then row order): the sort is
+ *     stable in both directions;
+ *   limit: the first `limit` rows of that order (ties by input order); < 0:
+ *     none; num_keys = 0: the first `limit` rows of the input as it is.
+ * `inputs`: num_batches >= 1 device batches of one schema (0-row batches
+ * allowed, sliced columns through dfmi_column.offset), all of which stay on
+ * the device; they are not copied into one batch. key_columns[k] indexes the
+ * batches' columns, key_asc[k] is 1 (ascending) or 0; at most 8 keys and fewer
+ * than 2^31 rows and Utf8 output bytes per column (else
+ * DFMI_ERR_NOT_IMPLEMENTED, "device program limit: ..."). `outputs`: one entry
+ * per input column, buffers sized by the caller for the total row count as
+ * dfmi_out_column says, validity for every column that has nulls in some
+ * batch, data_capacity >= the column's total input bytes. The library fills
+ * type, length = min(limit, total rows), null_count (exact; validity is
+ * written whenever some batch's column has nulls, bits past length in its
+ * last 64-bit word zero), data_length and passthrough_column = -1. The value
+ * bytes of null slots are unspecified. Synchronous. A missing flag, a key out
+ * of range or a NULL buffer is DFMI_ERR_INVALID_ARGUMENT.
+ * ------------------------------------------------------------------------- */
+int32_t dfmi_sort_batches(dfmi_context* ctx, const dfmi_batch* inputs, int32_t num_batches,
+                          const int32_t* key_columns, const int32_t* key_asc, int32_t num_keys,
+                          int64_t limit /* < 0: none */, dfmi_out_column* outputs,
+                          uint32_t flags, dfmi_error* err);
 
 /* ---------------------------------------------------------------------------
  * Multi-GPU. The reference is single-threaded (context.rs:33);

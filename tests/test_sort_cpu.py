@@ -1,0 +1,82 @@
+"""Sort / Limit extension (DFMI_FLAG_EXT_SORT), the parts that need no GPU:
+the ABI surface, the unchanged behaviour without the flag, the relations
+execute() builds with it, and the key-count program limit."""
+import os
+import re
+
+import pytest
+
+from datafusion_amd import _abi
+from datafusion_amd.arrow import Field, Schema
+from datafusion_amd.execution import (ExecutionContext, ExecutionError, LimitRelation, MemoryDataSource,
+                                      SortRelation)
+from datafusion_amd.execution import engine as engine_mod
+from datafusion_amd.execution.context import Limit, Projection, Sort, TableScan
+from datafusion_amd.logicalplan import Column, DataType, SortExpr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+PERSON = Schema([Field("id", DataType.Int64, False), Field("first_name", DataType.Utf8, True),
+                 Field("age", DataType.Float64, True)])
+
+
+def context(flags):
+    ctx = ExecutionContext(flags=flags)
+    ctx.register_datasource("person", MemoryDataSource(PERSON, []))
+    return ctx
+
+
+def test_flag_and_entry_point_are_declared_and_exported():
+    hdr = open(os.path.join(ROOT, "include", "dfmi.h")).read()
+    assert re.search(r"#define\s+DFMI_FLAG_EXT_SORT\s+0x20u", hdr)
+    assert re.search(r"int32_t\s+dfmi_sort_batches\s*\(", hdr)
+    assert re.search(r"#define DFMI_ABI_VERSION 4\b", hdr)
+    assert _abi.DFMI_FLAG_EXT_SORT == 0x20
+    assert _abi.DFMI_ABI_VERSION == 4
+    assert "dfmi_sort_batches" in _abi.EXPORTED
+    L = _abi.lib()
+    assert hasattr(L, "dfmi_sort_batches")
+    assert L.dfmi_abi_version() == 4
+
+
+@pytest.mark.parametrize("sql, node", [("SELECT id FROM person ORDER BY id", "Sort"),
+                                       ("SELECT id FROM person ORDER BY id LIMIT 10", "Limit"),
+                                       ("SELECT id FROM person LIMIT 10", "Limit")])
+def test_without_the_flag_sort_and_limit_stay_unimplemented(sql, node):
+    for flags in (0, _abi.DFMI_FLAG_EXT_AGGREGATE | _abi.DFMI_FLAG_EXT_GATHER_ALL):
+        with pytest.raises(ExecutionError) as e:
+            context(flags).sql(sql)
+        assert e.value.kind == "NotImplemented"
+        assert e.value.message == "unimplemented!() plan '%s'" % node
+
+
+def test_with_the_flag_execute_builds_the_relations_without_a_device():
+    before = dict(engine_mod._ENGINES)
+    ctx = context(_abi.DFMI_FLAG_EXT_SORT)
+    proj = Schema([PERSON.field(0)])
+    r = ctx.sql("SELECT id FROM person ORDER BY id")
+    assert type(r) is SortRelation and r.limit is None and r.schema() == proj
+    assert (r.key_columns, r.key_asc) == ([0], [True])
+    r = ctx.sql("SELECT id, age FROM person ORDER BY age DESC, id LIMIT 10")
+    assert type(r) is SortRelation and r.limit == 10
+    assert r.schema() == Schema([PERSON.field(0), PERSON.field(2)])
+    assert (r.key_columns, r.key_asc) == ([1, 0], [False, True])
+    r = ctx.sql("SELECT id FROM person LIMIT 10")
+    assert type(r) is LimitRelation and r.schema() == proj
+    # an expression key is a helper column behind the projection's
+    r = ctx.sql("SELECT id, age FROM person ORDER BY age + age")
+    assert r.key_columns == [2] and len(r.schema()) == 2
+    assert engine_mod._ENGINES == before  # nothing has asked for a device
+
+
+def test_more_than_eight_keys_is_a_program_limit():
+    ctx = context(_abi.DFMI_FLAG_EXT_SORT)
+    scan = TableScan("person", PERSON)
+    proj = Projection([Column(0)], scan, Schema([PERSON.field(0)]))
+    for plan in (Sort([SortExpr(Column(0), True)] * 9, proj, proj.schema),
+                 Limit(3, Sort([SortExpr(Column(0), i % 2 == 0) for i in range(9)], proj, proj.schema), proj.schema)):
+        with pytest.raises(ExecutionError) as e:
+            ctx.execute(plan)
+        assert e.value.kind == "NotImplemented"
+        assert e.value.message.startswith("device program limit: ")
+    assert type(ctx.execute(Sort([SortExpr(Column(0), True)] * 8, proj, proj.schema))) is SortRelation
