@@ -169,6 +169,8 @@ EXPORTED = [
     "dfmi_aggregate_free",
     "dfmi_agg_state_create",
     "dfmi_aggregate_batch",
+    "dfmi_aggregate_batches",
+    "dfmi_aggregate_host_batches",
     "dfmi_agg_state_finish",
     "dfmi_agg_partial_bytes",
     "dfmi_agg_state_partial",
@@ -351,6 +353,10 @@ def lib() -> C.CDLL:
     L.dfmi_agg_state_create.restype = C.c_int32
     L.dfmi_aggregate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(dfmi_batch), C.c_uint32, P(dfmi_error)]
     L.dfmi_aggregate_batch.restype = C.c_int32
+    for f in (L.dfmi_aggregate_batches, L.dfmi_aggregate_host_batches):
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(dfmi_batch), C.c_int32, C.c_uint32, P(C.c_int32),
+                      P(dfmi_error)]
+        f.restype = C.c_int32
     L.dfmi_agg_state_finish.argtypes = [C.c_void_p, C.c_void_p, P(dfmi_agg_value), P(dfmi_error)]
     L.dfmi_agg_state_finish.restype = C.c_int32
     L.dfmi_agg_state_create_grouped.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p), C.c_int32, P(C.c_void_p),

@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "agg_state.h"
+#include "batch_stage.h"
 #include "jit_skeleton.hip"
 
 using namespace dfmi;
@@ -46,6 +47,8 @@ void alloc_table(DevBuf& ctl, DevBuf& slot, gb::Table& t, uint64_t cap, hipStrea
     t.mask = cap - 1;
 }
 
+}  // namespace
+
 HashDev& hashdev(dfmi_context* ctx, dfmi_agg_state* st) {
     if (st->hd) return *st->hd;
     auto H = std::make_unique<HashDev>();
@@ -76,6 +79,8 @@ HashDev& hashdev(dfmi_context* ctx, dfmi_agg_state* st) {
     st->hd = std::move(H);
     return *st->hd;
 }
+
+namespace {
 
 void read_hdr(dfmi_context* ctx, HashDev& H) {
     HIP_TRY(hipMemcpyAsync(H.hh.p, H.hdr.p, sizeof(gb::Hdr), hipMemcpyDeviceToHost, ctx->stream));
@@ -384,12 +389,141 @@ void group_batch_on_host(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_progr
 // key's are merged on the host.
 void group_batch_hashed(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* in,
                         uint32_t flags, const AggDiag& diag) {
-    HashDev& H = hashdev(ctx, st);
     std::vector<dfmi::gb::Col> cols;
-    const bool prof = diag.finish_profile;
     const auto t0 = std::chrono::steady_clock::now();
     const int64_t m = eval_grouped(ctx, st, pred, in, flags, cols);
-    if (prof) HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (diag.finish_profile) HIP_TRY(hipStreamSynchronize(ctx->stream));
+    accumulate_hashed(ctx, st, cols, m, diag, t0);
+}
+
+// A coalesced call through the device hash table: the fused Selection +
+// Projection pass over [keys..., arguments...] as ONE launch
+// (filter_project_batches_staged) into per-batch segments of the state's
+// EvalOut buffers -- batch b's outputs at the worst-case row offset: the rows
+// before b, each batch rounded up to 64 -- then the segments packed dense
+// (k_group_concat; a pass-through output's source is the batch's own column)
+// and the table's passes run once over the call's selected rows.
+void group_batches_hashed(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* ins,
+                          int32_t nb_all, uint32_t flags, const AggDiag& diag, int32_t* failed) {
+    HashDev& H = hashdev(ctx, st);
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t nk = st->keys.size(), n = st->aggs.size();
+    const int no = (int)(nk + n);
+    // (dfmi_aggregate_batch skips a batch without rows: so does the call)
+    std::vector<dfmi_batch> live;
+    std::vector<int32_t> index;
+    for (int32_t b = 0; b < nb_all; ++b)
+        if (ins[b].num_rows > 0) {
+            live.push_back(ins[b]);
+            index.push_back(b);
+        }
+    const int32_t nb = (int32_t)live.size();
+    if (nb == 0) return;
+    if (nb > dfmi::gb::kConcatMaxBatches) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "too many batches in one hashed call"};
+    std::vector<const dfmi_program*> progs(no);
+    for (size_t p = 0; p < nk; ++p) progs[p] = &st->keys[p];
+    for (size_t j = 0; j < n; ++j) progs[nk + j] = &st->aggs[j]->arg;
+    std::vector<int64_t> seg(nb + 1, 0);
+    for (int32_t b = 0; b < nb; ++b) seg[b + 1] = seg[b] + (live[b].num_rows + 63) / 64 * 64;
+    const int64_t R = seg[nb];
+    std::vector<dfmi_out_column> outs((size_t)nb * no);
+    memset(outs.data(), 0, outs.size() * sizeof(dfmi_out_column));
+    for (int o = 0; o < no; ++o) {
+        const int t = progs[o]->type;
+        const int w = t == DFMI_TYPE_BOOLEAN ? 0 : std::max(jit::type_width(t), 1);
+        uint8_t* vals = (uint8_t*)H.bufs[HashDev::EvalOut + 2 * o].reserve(w ? (size_t)R * w : (size_t)R / 8);
+        uint8_t* valid = (uint8_t*)H.bufs[HashDev::EvalOut + 2 * o + 1].reserve((size_t)R / 8);
+        for (int32_t b = 0; b < nb; ++b) {
+            dfmi_out_column& c = outs[(size_t)b * no + o];
+            c.values = vals + (w ? (size_t)seg[b] * w : (size_t)seg[b] / 8);
+            c.validity = valid + (size_t)seg[b] / 8;
+        }
+    }
+    // no predicate and every key and argument a bare column: nothing to
+    // evaluate -- the first batch's pass raises what the plan raises (a
+    // static error) and names the pass-through columns, the same for every batch
+    bool bare = !pred;
+    for (const dfmi_program* p : progs) bare = bare && p->ir[p->root].kind == IR_COL;
+    dfmi_error e{};
+    int32_t fb = -1;
+    if (filter_project_batches_staged(ctx, pred, progs.data(), no, live.data(), bare ? 1 : nb, outs.data(), flags, &fb, &e,
+                                      nullptr) != DFMI_OK) {
+        st->failed = true;
+        st->failure = e;
+        if (fb >= 0) *failed = index[fb];
+        throw Fail{e.code, e.message};
+    }
+    for (int32_t b = 1; bare && b < nb; ++b)
+        for (int o = 0; o < no; ++o) {
+            dfmi_out_column& c = outs[(size_t)b * no + o];
+            c.passthrough_column = outs[o].passthrough_column;
+            if (c.passthrough_column < 0) throw Fail{DFMI_ERR_DEVICE, "GROUP BY: a bare column that is not passed through"};
+            if (!live[b].columns[c.passthrough_column].values)
+                throw Fail{DFMI_ERR_INVALID_ARGUMENT, "column values pointer is NULL"};
+            c.length = live[b].num_rows;
+        }
+    if (diag.finish_profile) HIP_TRY(hipStreamSynchronize(ctx->stream));
+    // ---- the per-batch segments packed dense
+    std::vector<long long> prefix(nb + 1, 0);
+    for (int32_t b = 0; b < nb; ++b) prefix[b + 1] = prefix[b] + outs[(size_t)b * no].length;
+    const int64_t m = prefix[nb];
+    std::vector<dfmi::gb::Col> cols(no, dfmi::gb::Col{});
+    if (m > 0) {
+        std::vector<unsigned long long> srcs;
+        std::vector<dfmi::gb::ConcatJob> jobs;
+        for (int o = 0; o < no; ++o) {
+            const int t = progs[o]->type;
+            dfmi::gb::Col& d = cols[o];
+            d.type = t;
+            d.width = t == DFMI_TYPE_BOOLEAN ? 0 : jit::type_width(t);
+            std::vector<unsigned long long> vsrc(nb), nsrc(nb);
+            bool any_nulls = false;
+            for (int32_t b = 0; b < nb; ++b) {
+                const dfmi_out_column& c = outs[(size_t)b * no + o];
+                if (c.passthrough_column >= 0) {
+                    const dfmi_column& src = live[b].columns[c.passthrough_column];
+                    vsrc[b] = (unsigned long long)src.values;
+                    nsrc[b] = src.validity && src.null_count > 0 ? (unsigned long long)src.validity : 0;
+                } else {
+                    vsrc[b] = (unsigned long long)c.values;
+                    nsrc[b] = c.null_count > 0 ? (unsigned long long)c.validity : 0;
+                }
+                any_nulls = any_nulls || nsrc[b];
+            }
+            void* dv = H.bufs[HashDev::PackOut + 2 * o].reserve(d.width ? (size_t)m * d.width : (size_t)(m + 63) / 64 * 8);
+            d.values = dv;
+            jobs.push_back(dfmi::gb::ConcatJob{dv, d.width, 0});
+            srcs.insert(srcs.end(), vsrc.begin(), vsrc.end());
+            if (any_nulls) {  // (a column with no nulls in any batch: no validity at all)
+                void* dn = H.bufs[HashDev::PackOut + 2 * o + 1].reserve((size_t)(m + 63) / 64 * 8);
+                d.validity = (const uint8_t*)dn;
+                jobs.push_back(dfmi::gb::ConcatJob{dn, 0, 0});
+                srcs.insert(srcs.end(), nsrc.begin(), nsrc.end());
+            }
+        }
+        // the pack kernel's table: [sources | jobs | prefix]
+        const size_t sb = srcs.size() * 8, jb = jobs.size() * sizeof(dfmi::gb::ConcatJob), pb = prefix.size() * 8;
+        uint8_t* tab = (uint8_t*)H.bufs[HashDev::PackTable].reserve(sb + jb + pb);
+        std::vector<uint8_t> htab(sb + jb + pb);
+        memcpy(htab.data(), srcs.data(), sb);
+        memcpy(htab.data() + sb, jobs.data(), jb);
+        memcpy(htab.data() + sb + jb, prefix.data(), pb);
+        HIP_TRY(hipMemcpyAsync(tab, htab.data(), htab.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));  // (htab is pageable: it must not go before the copy has read it)
+        HIP_TRY(dfmi::gb::launch_concat((const unsigned long long*)tab, (const dfmi::gb::ConcatJob*)(tab + sb),
+                                        (int)jobs.size(), (const long long*)(tab + sb + jb), nb, m, ctx->stream));
+        if (diag.finish_profile) HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    accumulate_hashed(ctx, st, cols, m, diag, t0);
+}
+
+// The m evaluated rows of `cols` (keys, then arguments: one batch's, or a
+// coalesced call's packed segments) through the table: claim with growth and
+// rerun, record and arena growth, normalisation, accumulate, the collision list.
+void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<dfmi::gb::Col>& cols, int64_t m,
+                       const AggDiag& diag, std::chrono::steady_clock::time_point t0) {
+    HashDev& H = hashdev(ctx, st);
+    const bool prof = diag.finish_profile;
     const auto t1 = std::chrono::steady_clock::now();
     if (m <= 0) return;
     if (m > 0x7fffffffll) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "GROUP BY batch of 2^31 selected rows or more"};

@@ -2,6 +2,7 @@
 // and what the device hash table's driver (agg_hash.cpp) offers the entry
 // points (aggregate.cpp).
 #pragma once
+#include <chrono>
 #include <cstdlib>
 #include <memory>
 #include <unordered_map>
@@ -99,6 +100,9 @@ struct HashDev {
         BucketRowGroup, BucketHist, BucketTotals, BucketPartGroup, BucketPartNull, BucketPartValues,
         // finish_device: the caller's arrays on the device; the radix sort's double buffers and scratch
         EmitKeys, EmitValues, EmitSortKeys, EmitSortKeys2, EmitSortVals, EmitSortVals2, EmitNullAt, EmitTemp,
+        // a coalesced call: the evaluation pass's per-batch segments packed dense, two per output column
+        // (values, validity); the pack kernel's source table, jobs and prefix
+        PackOut, PackTable = PackOut + 2 * (dfmi::gb::kMaxKeys + dfmi::gb::kMaxAggs),
         kSlots
     };
     DevBuf ctl, slot;                 // the table's storage; `t` views it
@@ -173,6 +177,9 @@ struct dfmi_agg_state {
     // over the batch's selected rows (a pre-pass through this same extension)
     dfmi_aggregate* mm[2] = {nullptr, nullptr};
     dfmi_agg_state* mm_state = nullptr;
+    // dfmi_aggregate_host_batches: the call's packed input columns, pinned and on the device
+    dfmi::agg::HostBuf<uint8_t> stage_host;
+    dfmi::agg::DevBuf stage_dev;
 };
 
 namespace dfmi {
@@ -214,11 +221,36 @@ inline void check_not_failed(const dfmi_agg_state* st) {
     if (st->failed) throw Fail{st->failure.code, st->failure.message};
 }
 
+// ---- aggregate.cpp: one aggregate batch's plan; the key window's flush
+// Static errors, slots and tile shape of one aggregate batch.
+struct AggBuilt {
+    xi::Err se;
+    jit::Plan plan;
+    jit::Launch X;
+    int64_t n_tiles = 0;
+};
+void build_agg_plan(const dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* in, uint32_t flags,
+                    const AggDiag& diag, AggBuilt& B, bool low_sel = false);
+void build_batch_plan(const dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* in, uint32_t flags,
+                      const AggDiag& diag, AggBuilt& B, bool low_sel);
+void flush_groups(dfmi_context* ctx, dfmi_agg_state* st);
+
+// ---- agg_batches.cpp: the coalesced entry points
+void count_query_launch();  // dfmi_internal_agg_query_launches
+
 // ---- agg_hash.cpp: the device hash table's driver
+HashDev& hashdev(dfmi_context* ctx, dfmi_agg_state* st);
+void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<dfmi::gb::Col>& cols, int64_t m,
+                       const AggDiag& diag, std::chrono::steady_clock::time_point t0);
 void group_batch_on_host(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* in,
                          uint32_t flags);
 void group_batch_hashed(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* in,
                         uint32_t flags, const AggDiag& diag);
+// ... nb batches (offset-0 columns, fixed-width and Boolean keys and arguments, at most
+// gb::kConcatMaxBatches) as one evaluation launch and one run of the table's passes; *failed: the
+// first failing batch (the state is failed and the error thrown).
+void group_batches_hashed(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* ins,
+                          int32_t nb, uint32_t flags, const AggDiag& diag, int32_t* failed);
 void reset_table(dfmi_context* ctx, HashDev& H);
 void unflatten(dfmi_agg_state* st);
 void drain_hashed(dfmi_context* ctx, dfmi_agg_state* st);

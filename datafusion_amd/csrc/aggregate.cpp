@@ -13,7 +13,8 @@
 // This file: the ungrouped and key-window path and the entry points. The
 // arithmetic, the host group map and the partials' wire format are
 // agg_host.cpp (no device in it); the device hash table's driver is
-// agg_hash.cpp; the state they share is agg_state.h.
+// agg_hash.cpp; the coalesced entry points (many batches per call) are
+// agg_batches.cpp; the state they share is agg_state.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,20 +34,14 @@ using namespace dfmi::xi;
 using namespace dfmi::aggh;
 using namespace dfmi::agg;
 
-namespace {
+namespace dfmi {
+namespace agg {
 
-// Static errors, slots and tile shape of one aggregate batch (the filtered
-// form of exec.cpp's build_plan: FilterRelation::next, then each argument
-// over the filtered batch in aggregate order).
-struct AggBuilt {
-    Err se;
-    jit::Plan plan;
-    jit::Launch X;
-    int64_t n_tiles = 0;
-};
-
+// Static errors, slots and tile shape of one aggregate batch (AggBuilt,
+// agg_state.h: the filtered form of exec.cpp's build_plan: FilterRelation::next,
+// then each argument over the filtered batch in aggregate order).
 void build_agg_plan(const dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* in, uint32_t flags,
-                    const AggDiag& diag, AggBuilt& B, bool low_sel = false) {
+                    const AggDiag& diag, AggBuilt& B, bool low_sel) {
     Err& se = B.se;
     jit::Launch& X = B.X;
     const int64_t n = in->num_rows;
@@ -157,6 +152,11 @@ void build_batch_plan(const dfmi_agg_state* st, const dfmi_program* pred, const 
     }
 }
 
+}  // namespace agg
+}  // namespace dfmi
+
+namespace {
+
 std::vector<Partial> merge_copies(const dfmi_agg_state* st, const std::vector<uint64_t>& h) {
     const size_t n = st->aggs.size();
     std::vector<Partial> parts(n);
@@ -176,9 +176,11 @@ std::vector<uint64_t> read_acc(dfmi_context* ctx, dfmi_agg_state* st) {
     return h;
 }
 
+}  // namespace
+
 // GROUP BY: the device window accumulators (win_base / win_width) merged into
 // the host's groups, and the device window state reset.
-void flush_groups(dfmi_context* ctx, dfmi_agg_state* st) {
+void dfmi::agg::flush_groups(dfmi_context* ctx, dfmi_agg_state* st) {
     if (!st->dirty) return;
     const std::vector<uint64_t> h = read_acc(ctx, st);
     const size_t n = st->aggs.size(), na = n + 1;
@@ -204,6 +206,8 @@ void flush_groups(dfmi_context* ctx, dfmi_agg_state* st) {
     HIP_TRY(hipMemcpyAsync(st->acc.p, st->init.data(), st->acc_words * 8, hipMemcpyHostToDevice, ctx->stream));
     st->dirty = false;
 }
+
+namespace {
 
 // Every group the state holds (window, hash table, host merges) in st->groups.
 void collect_groups(dfmi_context* ctx, dfmi_agg_state* st) {
@@ -240,7 +244,11 @@ int64_t agg_jit_source(const dfmi_program* pred, const dfmi_program* key, const 
     }
     for (int j = 0; j < n; ++j) st.aggs.push_back(aggs[j]);
     AggBuilt B;
-    build_agg_plan(&st, pred, in, flags, agg_diag(), B);
+    build_agg_plan(&st, pred, in, flags & ~0x40000000u, agg_diag(), B);
+    if (flags & 0x40000000u) {  // the coalesced-batches form of the kernel (agg_batches.cpp)
+        B.X.batched = true;
+        B.X.M = 1;
+    }
     const std::string src = jit::generate(B.plan, B.X);
     if (compile) (void)jit::compile_code(src, nullptr);
     if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", src.c_str());
@@ -518,6 +526,7 @@ extern "C" int32_t dfmi_aggregate_batch(dfmi_context* ctx, dfmi_agg_state* st, c
             A.gwidth = st->win_width;
             HIP_TRY(hipEventRecord(ctx->ev0, stream));
             launch_query(fn, (unsigned)B.n_tiles, X.BLOCK, A, stream);
+            count_query_launch();
             ws_commit(ctx, ws);
             HIP_TRY(hipEventRecord(ctx->ev1, stream));
             HIP_TRY(hipMemcpyAsync(ctx->host_hdr, ws.hdr, kHdrAlloc, hipMemcpyDeviceToHost, stream));
@@ -634,6 +643,8 @@ int32_t dfmi_agg_state_show_merged(dfmi_agg_state* st, const void* const* partia
 // Internal test hook (not part of the C ABI, not declared in include/): the
 // aggregate kernel a dfmi_aggregate_batch call would launch, generated and
 // (compile != 0) compiled with hipRTC -- no device needed (tests/test_aggregate_cpu.py).
+// Flag bit 0x40000000 (as dfmi_internal_jit_check): the batched form a
+// dfmi_aggregate_batches call launches (tests/test_agg_batches_cpu.py).
 // Diagnostics: grouped batches accumulated by the bucketed passes (groupby.h) in this process.
 extern "C" long dfmi_internal_group_bucketed_batches() { return bucketed_batches(); }
 

@@ -238,6 +238,23 @@ struct EmitArgs {
 hipError_t launch_emit(EmitArgs a, unsigned long long* sk, unsigned long long* sk2, unsigned* sv, unsigned* sv2,
                        unsigned* null_at, void* tmp, size_t* tmp_bytes, hipStream_t stream);
 
+// Coalesced batches (agg_batches.cpp): the evaluation pass leaves every
+// output column in per-batch segments; one pack job per buffer (a column's
+// values, or its validity) copies the segments' rows into one dense buffer,
+// so the passes above run once over the call's m rows. Dense row i belongs to
+// batch b with prefix[b] <= i < prefix[b + 1] (binary search over the prefix,
+// held in LDS) and is row i - prefix[b] of srcs[job * nb + b]. width > 0:
+// fixed-width values; width == 0: bits (Boolean values, validity) -- one wave
+// per 64 dense rows assembles its word with a ballot; a null source: ones.
+constexpr int kConcatMaxBatches = 1024;
+struct ConcatJob {
+    void* dst;
+    int width;
+    int pad;
+};
+hipError_t launch_concat(const unsigned long long* srcs, const ConcatJob* jobs, int njobs, const long long* prefix,
+                         int nb, long long m, hipStream_t stream);
+
 // groupby.hip: launches on `stream` (asynchronous)
 hipError_t launch_claim(const ClaimArgs& a, hipStream_t stream);
 hipError_t launch_accumulate(const AccArgs& a, hipStream_t stream);

@@ -1184,6 +1184,50 @@ __global__ __launch_bounds__(256) void k_group_emit(const EmitArgs A) {
     }
 }
 
+// The per-batch segments of one buffer packed into a dense one (groupby.h
+// ConcatJob): blockIdx.y is the job; a wave takes 64 consecutive dense rows
+// at a time, so fixed-width stores coalesce and a bits job's wave owns whole
+// destination words.
+__global__ __launch_bounds__(256) void k_group_concat(const u64* srcs, const ConcatJob* jobs, const long long* prefix,
+                                                      int nb, long long m) {
+    __shared__ long long P[kConcatMaxBatches + 1];
+    for (int i = threadIdx.x; i <= nb; i += blockDim.x) P[i] = prefix[i];
+    __syncthreads();
+    const ConcatJob job = jobs[blockIdx.y];
+    const u64* src = srcs + (size_t)blockIdx.y * nb;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    // (the loop bound is uniform over a wave: every lane takes part in the ballot)
+    for (long long r0 = (long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63); r0 < m; r0 += stride) {
+        const long long i = r0 + (threadIdx.x & 63);
+        const bool in = i < m;
+        int b = 0;
+        long long local = 0;
+        if (in) {
+            int lo = 0, hi = nb - 1;  // the last b with P[b] <= i (empty batches repeat a prefix: the last one wins)
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (P[mid] <= i) lo = mid;
+                else hi = mid - 1;
+            }
+            b = lo;
+            local = i - P[b];
+        }
+        const unsigned char* sp = (const unsigned char*)src[b];
+        if (job.width == 0) {
+            const bool bit = in && (!sp || ((sp[local >> 3] >> (local & 7)) & 1));
+            const u64 w = __ballot(bit);
+            if ((threadIdx.x & 63) == 0) ((u64*)job.dst)[r0 >> 6] = w;
+        } else if (in) {
+            switch (job.width) {
+                case 1: ((unsigned char*)job.dst)[i] = sp[local]; break;
+                case 2: ((unsigned short*)job.dst)[i] = ((const unsigned short*)sp)[local]; break;
+                case 4: ((unsigned*)job.dst)[i] = ((const unsigned*)sp)[local]; break;
+                default: ((u64*)job.dst)[i] = ((const u64*)sp)[local]; break;
+            }
+        }
+    }
+}
+
 static int grid_for(long long items, int per_block = 256, int cap = 8192) {
     long long g = (items + per_block - 1) / per_block;
     return (int)(g < 1 ? 1 : (g > cap ? cap : g));
@@ -1210,6 +1254,14 @@ hipError_t launch_accumulate(const AccArgs& a, hipStream_t st) {
         case 4: hipLaunchKernelGGL(k_group_accumulate<4>, g, b, 0, st, a); break;
         default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_concat(const unsigned long long* srcs, const ConcatJob* jobs, int njobs, const long long* prefix,
+                         int nb, long long m, hipStream_t st) {
+    if (nb < 1 || nb > kConcatMaxBatches || njobs < 1) return hipErrorInvalidValue;
+    if (m <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_group_concat, dim3(grid_for(m, 256, 2048), njobs), dim3(256), 0, st, srcs, jobs, prefix, nb, m);
     return hipGetLastError();
 }
 

@@ -799,7 +799,8 @@ static void generate_agg(Gen& g, std::ostringstream& o, const Plan& P, Launch& X
     // global atomic per 64 blocks -- a counter every wave hit would serialise)
     if (P.pred) o << "  if (lane == 0 && nsel_) atomicAdd(&NSEL_, nsel_);\n";
     o << "  dfmi::lds_sync();\n  dfmi::agg_block_flush<NA, NF>(A, S, fslot, is_min, tid);\n";
-    if (P.pred) o << "  if (tid == 0 && NSEL_ && (blockIdx.x & 63u) == 0) atomicAdd(A.totals, (u64)NSEL_);\n";
+    // (the coalesced form feeds no selectivity hint: nothing is written to the batch's totals)
+    if (P.pred && !X.batched) o << "  if (tid == 0 && NSEL_ && (blockIdx.x & 63u) == 0) atomicAdd(A.totals, (u64)NSEL_);\n";
     if (!(X.M > 1 && P.pred)) o << "  }\n";
 }
 
@@ -922,7 +923,7 @@ static void emit_batched_prologue(std::ostream& o, const Plan& P, const Launch& 
       // diagnostics (mode bit 4): the forced look-back timeout in the first
       // batch's own error word, which the coalesced launch's host reads
       << "  if ((A.mode & 16) && blockIdx.x == 0 && tid == 0) atomicMax(A.err, ~(u64)3);\n";
-    if (P.pred)  // [ch][tile] status words of this batch's tiles
+    if (P.pred && P.aggs.empty())  // [ch][tile] status words of this batch's tiles
         o << "  A.status = A0.status + (i64)(tt_ >> 32) * " << (1 + X.utf8_outs.size()) * (size_t)X.spread << ";\n";
     for (size_t s = 0; s < X.num_cols.size(); ++s)
         o << "  A.col[" << s << "] = bp_[" << batch_slot_col((int)s) << "];\n  A.valid[" << s << "] = (const u8*)bp_["
@@ -958,7 +959,8 @@ std::string generate(const Plan& P, Launch& X) {
     else
         o << "  const unsigned bid_ = blockIdx.x;\n";
     if (X.batched) {
-        if (!P.aggs.empty()) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "batched launch of an aggregate"};
+        // (an aggregate: zero outputs in the table; A.agg, gbase and gwidth stay the call's)
+        if (!P.aggs.empty() && X.M != 1) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "batched aggregate with sub-tiles"};
         emit_batched_prologue(o, P, X);
     } else {
         o << "  const dfmi::Args& A = A0;\n  const unsigned tile_ = bid_;\n";

@@ -137,6 +137,8 @@ class ExecutionContext:
         (dfmi_filter_project_batches / dfmi_filter_project_host_batches), still
         returning one output batch per input batch -- at csv_sql.rs:49's
         1024-row batches one call per batch would cost a GPU round trip each.
+        An Aggregate reads ahead the same way and accumulates each group with
+        one dfmi_aggregate_batches / dfmi_aggregate_host_batches call.
         coalesce=1: one call per pull."""
         self.datasources: Dict[str, object] = {}
         self.device = device
@@ -223,4 +225,5 @@ class ExecutionContext:
             fields.append(Field(k.get_name(), DataType(k.get_type()), True))
         aggs = [compile_expr(self, e, input_schema, self.flags) for e in plan.aggr_expr]
         fields += [Field(e.name, e.return_type, True) for e in plan.aggr_expr]  # sqlplanner.rs:385-389
-        return AggregateRelation(source, pred, aggs, Schema(fields), self.device, self.flags, keys or None)
+        return AggregateRelation(source, pred, aggs, Schema(fields), self.device, self.flags, keys or None,
+                                 coalesce=self.coalesce)

@@ -74,6 +74,10 @@ class DeviceEngine:
             return None
         return t.value, m.value
 
+    def current_stream(self) -> int:
+        """The calling thread's current stream on this device (its handle)."""
+        return torch.cuda.current_stream(self.device).cuda_stream
+
     def to_device(self, batch: RecordBatch) -> RecordBatch:
         if all(c.values.device == self.device for c in batch.columns):
             return batch
@@ -512,6 +516,50 @@ class AggState:
                                     C.byref(cb), flags, C.byref(err))
         if rc != _abi.DFMI_OK:
             raise ExecutionError.from_status(rc, err.message.decode("utf-8", errors="replace"))
+
+    def add_many(self, predicate, batches: Sequence[RecordBatch], flags: int = 0) -> None:
+        """Many small batches in one call each per run of device batches
+        (dfmi_aggregate_batches) or host batches (dfmi_aggregate_host_batches):
+        the state and the error are those of add() on every batch in order
+        (the error carries `failed_batch`, its index in `batches`)."""
+        self.eng.drain()
+        self._add_runs(predicate, batches, flags)
+
+    def _add_runs(self, predicate, batches, flags: int = 0, stream=None) -> None:
+        """add_many without the drain (AggregateRelation runs it as the
+        engine's in-flight call, on `stream`: the pulling thread's)."""
+        batches = list(batches)
+        i = 0
+        while i < len(batches):
+            host = all(c.values.is_cpu for c in batches[i].columns)
+            j = i + 1
+            while j < len(batches) and all(c.values.is_cpu for c in batches[j].columns) == host:
+                j += 1
+            self._add_run(predicate, batches[i:j], flags, host, i, stream)
+            i = j
+
+    def _add_run(self, predicate, run, flags: int, host: bool, first: int, stream=None) -> None:
+        eng = self.eng
+        L = _abi.lib()
+        nb = len(run)
+        if host:
+            cb, keep = host_batch_structs(run, len(run[0].columns))
+        else:
+            keep = [eng._batch_struct(b) for b in run]
+            cb = (_abi.dfmi_batch * nb)(*[k[0] for k in keep])
+        err = _abi.dfmi_error()
+        failed = C.c_int32(-1)
+        if stream is None:
+            stream = torch.cuda.current_stream(eng.device).cuda_stream
+        L.dfmi_context_set_stream(eng.ctx, C.c_void_p(stream))
+        fn = L.dfmi_aggregate_host_batches if host else L.dfmi_aggregate_batches
+        rc = fn(eng.ctx, self.handle, predicate.handle if predicate is not None else None, cb, nb, flags,
+                C.byref(failed), C.byref(err))
+        del keep
+        if rc != _abi.DFMI_OK:
+            e = ExecutionError.from_status(rc, err.message.decode("utf-8", errors="replace"))
+            e.failed_batch = first + failed.value if failed.value >= 0 else -1
+            raise e
 
     def reset(self) -> None:
         self.eng.drain()

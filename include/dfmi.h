@@ -480,6 +480,35 @@ int32_t dfmi_agg_state_create(dfmi_context* ctx, const dfmi_aggregate* const* ag
  * except for error reporting, which is synchronous like dfmi_filter_project. */
 int32_t dfmi_aggregate_batch(dfmi_context* ctx, dfmi_agg_state* state, const dfmi_program* predicate,
                              const dfmi_batch* input, uint32_t flags, dfmi_error* err);
+/* Many small batches (the reference's 1024-row Relation::next pulls) in ONE
+ * call: the state afterwards is the state after dfmi_aggregate_batch on
+ * inputs[0..num_batches) in order, bit for bit, for ungrouped and for grouped
+ * states. Ungrouped states and one narrow Boolean / integer key run as one
+ * batch-table copy, one launch of the batched aggregate kernel (a coalesced
+ * MIN / MAX pre-pass finds one key window for the whole call), one copy of
+ * the per-batch headers and one synchronisation. Hash-table states (wide
+ * integer, float or several keys) evaluate the keys and arguments of every
+ * batch in one launch and run the table's passes once over the call's
+ * selected rows. A state whose predicate, keys or arguments read a Utf8
+ * column runs the call one batch at a time, with the same results and errors. num_batches == 0 is a no-op; 0-row batches, sliced
+ * columns and batches that differ in nullability are allowed; batches must
+ * share column types (DFMI_ERR_INVALID_ARGUMENT "batches do not share a
+ * schema"). On an error the call returns the error of the first batch, in
+ * order, on which dfmi_aggregate_batch would have failed, *failed_batch
+ * (may be NULL) names it (-1 otherwise) and the state is failed, as after a
+ * failing dfmi_aggregate_batch. */
+int32_t dfmi_aggregate_batches(dfmi_context* ctx, dfmi_agg_state* state, const dfmi_program* predicate,
+                               const dfmi_batch* inputs, int32_t num_batches, uint32_t flags,
+                               int32_t* failed_batch, dfmi_error* err);
+/* ... over HOST batches (inputs hold host pointers): the columns the
+ * predicate, the keys and the arguments read are packed into pinned staging,
+ * moved with one copy and run through the device form; nothing but the
+ * per-batch headers comes back. A call whose needed bytes exceed the staging
+ * budget (64 MiB) is split at batch boundaries into consecutive sub-calls; a
+ * single over-size batch is staged alone. */
+int32_t dfmi_aggregate_host_batches(dfmi_context* ctx, dfmi_agg_state* state, const dfmi_program* predicate,
+                                    const dfmi_batch* inputs, int32_t num_batches, uint32_t flags,
+                                    int32_t* failed_batch, dfmi_error* err);
 /* The aggregate values over every batch so far (num_aggs entries). */
 int32_t dfmi_agg_state_finish(dfmi_context* ctx, dfmi_agg_state* state, dfmi_agg_value* out,
                               dfmi_error* err);
