@@ -109,10 +109,10 @@ Failure run_batched(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* p
         const int NPW = jit::batch_words(X, 0);
         const size_t table_bytes = (size_t)nb * NPW * 8, meta_bytes = table_bytes + (size_t)T * 4;
         const size_t hdr_bytes = (size_t)nb * kBatchHdr;
-        ensure_host(&ctx->host_bmeta, &ctx->host_bmeta_bytes, meta_bytes);
-        ensure(ctx, &ctx->bmeta, &ctx->bmeta_bytes, meta_bytes);
-        ensure_host(&ctx->host_bhdr, &ctx->host_bhdr_bytes, hdr_bytes);
-        ensure(ctx, &ctx->bhdr, &ctx->bhdr_bytes, hdr_bytes);
+        ctx->host_bmeta.resize(meta_bytes, kCtxPinned);
+        ctx->host_bhdr.resize(hdr_bytes, kCtxPinned);
+        uint8_t* const bmeta = (uint8_t*)ctx->bmeta.reserve(meta_bytes, kCtxDev);
+        uint8_t* const bhdr = (uint8_t*)ctx->bhdr.reserve(hdr_bytes, kCtxDev);
         bool need_ones = false;
         for (int i = 0; i < ncols && !need_ones; ++i)
             if (nullable[i])
@@ -120,36 +120,36 @@ Failure run_batched(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* p
                     if (!(ins[b].columns[i].validity && ins[b].columns[i].null_count > 0)) need_ones = true;
         if (need_ones) {  // the all-valid bitmap of the batches without nulls in a column others have them in
             const size_t nbm = (size_t)((maxn + 63) / 64 * 8 + 64);
-            if (ctx->ones_bytes < nbm) {
-                ensure(ctx, &ctx->ones, &ctx->ones_bytes, nbm);
-                HIP_TRY(hipMemsetAsync(ctx->ones, 0xff, ctx->ones_bytes, stream));
+            if (ctx->ones.cap < nbm) {
+                ctx->ones.reserve(nbm, kCtxDev);
+                HIP_TRY(hipMemsetAsync(ctx->ones.p, 0xff, ctx->ones.cap, stream));
             }
         }
-        uint64_t* tab = (uint64_t*)ctx->host_bmeta;
-        int32_t* tile_batch = (int32_t*)(ctx->host_bmeta + table_bytes);
+        uint64_t* tab = (uint64_t*)ctx->host_bmeta.p;
+        int32_t* tile_batch = (int32_t*)(ctx->host_bmeta.p + table_bytes);
         for (int32_t b = 0; b < nb; ++b) {
             const dfmi_batch& in = ins[b];
             uint64_t* row = tab + (size_t)b * NPW;
             memset(row, 0, (size_t)NPW * 8);
             row[0] = (uint64_t)in.num_rows;
             row[1] = (uint64_t)tiles[b] | ((uint64_t)first[b] << 32);
-            row[2] = (uint64_t)(ctx->bhdr + (size_t)b * kBatchHdr);
-            row[3] = (uint64_t)(ctx->bhdr + (size_t)b * kBatchHdr + kBatchHdrErrWord * 8);
+            row[2] = (uint64_t)(bhdr + (size_t)b * kBatchHdr);
+            row[3] = (uint64_t)(bhdr + (size_t)b * kBatchHdr + kBatchHdrErrWord * 8);
             for (size_t sl = 0; sl < X.num_cols.size(); ++sl) {
                 const int col = X.num_cols[sl];
                 const dfmi_column& c = in.columns[col];
-                const int w = jit::type_width(c.type);
+                const int w = dfmi::type_width(c.type);
                 if (in.num_rows > 0 && !c.values) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "column values pointer is NULL"};
                 if (w && ((uintptr_t)c.values & (w - 1)))
                     throw Fail{DFMI_ERR_INVALID_ARGUMENT, "column values must be aligned to their width"};
                 row[jit::batch_slot_col((int)sl)] = (uint64_t)c.values;
                 row[jit::batch_slot_col((int)sl) + 1] =
-                    !nullable[col] ? 0 : (uint64_t)((c.validity && c.null_count > 0) ? c.validity : ctx->ones);
+                    !nullable[col] ? 0 : (uint64_t)((c.validity && c.null_count > 0) ? c.validity : ctx->ones.p);
             }
             for (int64_t t = 0; t < tiles[b]; ++t) tile_batch[first[b] + t] = b;
         }
-        HIP_TRY(hipMemcpyAsync(ctx->bmeta, ctx->host_bmeta, meta_bytes, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemsetAsync(ctx->bhdr, 0, hdr_bytes, stream));
+        HIP_TRY(hipMemcpyAsync(bmeta, ctx->host_bmeta.p, meta_bytes, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(bhdr, 0, hdr_bytes, stream));
         Args A;
         memset(&A, 0, sizeof A);
         A.n_rows = maxn;
@@ -157,8 +157,8 @@ Failure run_batched(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* p
         bind_literals(A, X);
         const WsLease ws = ws_acquire(ctx, 0, stream);
         bind_workspace(A, ws);
-        A.tile_batch = (const int*)(ctx->bmeta + table_bytes);
-        A.batch_ptrs = (void* const*)ctx->bmeta;
+        A.tile_batch = (const int*)(bmeta + table_bytes);
+        A.batch_ptrs = (void* const*)bmeta;
         A.agg = st->acc.as<unsigned long long>();
         A.gbase = st->win_base;
         A.gwidth = st->win_width;
@@ -167,7 +167,7 @@ Failure run_batched(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* p
         count_query_launch();
         ws_commit(ctx, ws);
         if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev1, stream));
-        HIP_TRY(hipMemcpyAsync(ctx->host_bhdr, ctx->bhdr, hdr_bytes, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(ctx->host_bhdr.p, bhdr, hdr_bytes, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         if (ctx->timing) {
             float m1 = 0;
@@ -175,7 +175,7 @@ Failure run_batched(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* p
             ctx->last_main_ms = ctx->last_total_ms = m1;
             ctx->timed = true;
         }
-        host_hdr = ctx->host_bhdr;
+        host_hdr = ctx->host_bhdr.p;
     }
     // ---- in batch order: the first batch dfmi_aggregate_batch would have failed on
     const Err& se = B.se;
@@ -297,19 +297,6 @@ bool reads_utf8(const dfmi_program* p) {
     return false;
 }
 
-void check_shared_schema(const dfmi_batch* ins, int32_t nb) {
-    const int ncols = ins[0].num_columns;
-    for (int32_t b = 0; b < nb; ++b) {
-        if (ins[b].num_columns != ncols || (ncols > 0 && !ins[b].columns))
-            throw Fail{DFMI_ERR_INVALID_ARGUMENT, "batches do not share a schema"};
-        for (int i = 0; i < ncols; ++i) {
-            if (ins[b].columns[i].type != ins[0].columns[i].type)
-                throw Fail{DFMI_ERR_INVALID_ARGUMENT, "batches do not share a schema"};
-            if (ins[b].columns[i].length != ins[b].num_rows) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "ragged batch"};
-        }
-    }
-}
-
 // The device form's body (the arguments checked, the schema shared).
 void aggregate_batches(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* ins, int32_t nb,
                        uint32_t flags, int32_t* failed) {
@@ -342,33 +329,10 @@ void aggregate_batches(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program
     }
 }
 
-size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
-
-// Columns the predicate, the keys and the arguments read.
-void mark_columns(const dfmi_program* p, std::vector<char>& need) {
-    if (!p) return;
-    for (const IrNode& nd : p->ir)
-        if (nd.kind == IR_COL && nd.col >= 0 && nd.col < (int)need.size()) need[nd.col] = 1;
-}
-
-// Bytes of a needed host column's buffers in the staging block: values, validity, offsets.
-struct ColBytes {
-    size_t values = 0, validity = 0, offsets = 0;
-    size_t total() const { return align64(values) + align64(validity) + align64(offsets); }
-};
-
-ColBytes col_bytes(const dfmi_column& c, int64_t n) {
-    ColBytes cb;
-    if (n <= 0) return cb;
-    if (c.type == DFMI_TYPE_UTF8) {
-        cb.offsets = (size_t)(n + 1) * 4;
-        cb.values = c.offsets ? (size_t)std::max(0, c.offsets[n]) : 0;
-    } else if (c.type == DFMI_TYPE_BOOLEAN) {
-        cb.values = (size_t)(n + 7) / 8;
-    } else {
-        cb.values = (size_t)n * (size_t)std::max(1, jit::type_width(c.type));
-    }
-    if (c.validity && c.null_count > 0) cb.validity = (size_t)(n + 7) / 8;
+// Bytes of a needed host column's buffers in the staging block (a bitmap without nulls is not staged).
+ColBytes staged_bytes(const dfmi_column& c, int64_t n) {
+    ColBytes cb = n > 0 ? col_bytes(c, n) : ColBytes{};
+    if (c.null_count <= 0) cb.validity = 0;
     return cb;
 }
 
@@ -385,7 +349,7 @@ extern "C" int32_t dfmi_aggregate_batches(dfmi_context* ctx, dfmi_agg_state* st,
     return guarded(err, [&]() -> int32_t {
         if (!ctx || !st || nb < 0 || (nb > 0 && !ins)) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         if (nb == 0) return DFMI_OK;
-        check_shared_schema(ins, nb);
+        check_shared_schema(ins, nb, false);
         aggregate_batches(ctx, st, pred, ins, nb, flags, failed);
         return DFMI_OK;
     });
@@ -400,7 +364,7 @@ extern "C" int32_t dfmi_aggregate_host_batches(dfmi_context* ctx, dfmi_agg_state
     return guarded(err, [&]() -> int32_t {
         if (!ctx || !st || nb < 0 || (nb > 0 && !ins)) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         if (nb == 0) return DFMI_OK;
-        check_shared_schema(ins, nb);
+        check_shared_schema(ins, nb, false);
         check_not_failed(st);
         Unsliced us_;
         if (any_offset(ins, nb)) ins = unslice(ins, nb, us_, false, nullptr);
@@ -423,7 +387,8 @@ extern "C" int32_t dfmi_aggregate_host_batches(dfmi_context* ctx, dfmi_agg_state
                     if (!need[i]) continue;
                     if (ins[b1].num_rows > 0 && (!c.values || (c.type == DFMI_TYPE_UTF8 && !c.offsets)))
                         throw Fail{DFMI_ERR_INVALID_ARGUMENT, "column values pointer is NULL"};
-                    bb += col_bytes(c, ins[b1].num_rows).total();
+                    const ColBytes cb = staged_bytes(c, ins[b1].num_rows);
+                    bb += align64(cb.values) + align64(cb.validity) + align64(cb.offsets);
                 }
                 if (b1 > b0 && bytes + bb > kStageBudget) break;
                 bytes += bb;
@@ -455,7 +420,7 @@ extern "C" int32_t dfmi_aggregate_host_batches(dfmi_context* ctx, dfmi_agg_state
                     d.values = dbase;  // (a column nothing reads: its type and length only)
                     d.offsets = c.type == DFMI_TYPE_UTF8 ? (const int32_t*)dbase : nullptr;
                     if (!need[i]) continue;
-                    const ColBytes cb = col_bytes(c, n);
+                    const ColBytes cb = staged_bytes(c, n);
                     d.values = put(c.values, cb.values);
                     if (cb.validity) {
                         d.validity = put(c.validity, cb.validity);

@@ -136,7 +136,7 @@ int64_t eval_grouped(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* 
             c.data = (uint8_t*)H.bufs[HashDev::EvalOut + bi++].reserve(cap);
             c.data_capacity = (int64_t)cap;
         } else {
-            const int w = jit::type_width(t);
+            const int w = dfmi::type_width(t);
             c.values = H.bufs[HashDev::EvalOut + bi++].reserve(t == DFMI_TYPE_BOOLEAN ? (size_t)(rows + 63) / 64 * 8 : (size_t)rows * std::max(w, 1));
         }
         c.validity = (uint8_t*)H.bufs[HashDev::EvalOut + bi++].reserve((size_t)(rows + 63) / 64 * 8);
@@ -152,7 +152,7 @@ int64_t eval_grouped(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* 
         const dfmi_out_column& c = outs[o];
         dfmi::gb::Col& d = cols[o];
         d.type = progs[o]->type;
-        d.width = d.type == DFMI_TYPE_UTF8 || d.type == DFMI_TYPE_BOOLEAN ? 0 : jit::type_width(d.type);
+        d.width = d.type == DFMI_TYPE_UTF8 || d.type == DFMI_TYPE_BOOLEAN ? 0 : dfmi::type_width(d.type);
         if (c.passthrough_column >= 0) {
             const dfmi_column& src = in->columns[c.passthrough_column];
             d.values = src.values;
@@ -430,7 +430,7 @@ void group_batches_hashed(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_prog
     memset(outs.data(), 0, outs.size() * sizeof(dfmi_out_column));
     for (int o = 0; o < no; ++o) {
         const int t = progs[o]->type;
-        const int w = t == DFMI_TYPE_BOOLEAN ? 0 : std::max(jit::type_width(t), 1);
+        const int w = t == DFMI_TYPE_BOOLEAN ? 0 : std::max(dfmi::type_width(t), 1);
         uint8_t* vals = (uint8_t*)H.bufs[HashDev::EvalOut + 2 * o].reserve(w ? (size_t)R * w : (size_t)R / 8);
         uint8_t* valid = (uint8_t*)H.bufs[HashDev::EvalOut + 2 * o + 1].reserve((size_t)R / 8);
         for (int32_t b = 0; b < nb; ++b) {
@@ -475,7 +475,7 @@ void group_batches_hashed(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_prog
             const int t = progs[o]->type;
             dfmi::gb::Col& d = cols[o];
             d.type = t;
-            d.width = t == DFMI_TYPE_BOOLEAN ? 0 : jit::type_width(t);
+            d.width = t == DFMI_TYPE_BOOLEAN ? 0 : dfmi::type_width(t);
             std::vector<unsigned long long> vsrc(nb), nsrc(nb);
             bool any_nulls = false;
             for (int32_t b = 0; b < nb; ++b) {
@@ -563,14 +563,14 @@ void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<
     if (ng > H.acc_cap) {
         uint64_t want = H.acc_cap;
         while (want < ng) want *= 2;
-        H.acc.regrow(ctx, H.acc_cap * (size_t)H.words * 8, want * (size_t)H.words * 8);
+        H.acc.regrow(ctx->stream, H.acc_cap * (size_t)H.words * 8, want * (size_t)H.words * 8);
         HIP_TRY(dfmi::gb::launch_init(H.records(), H.pattern.as<unsigned long long>(), H.words, H.acc_cap, want, stream));
         H.acc_cap = want;
     }
     if (aend > H.arena_cap) {
         uint64_t want = H.arena_cap;
         while (want < aend) want *= 2;
-        H.arena.regrow(ctx, H.arena_cap, want);
+        H.arena.regrow(ctx->stream, H.arena_cap, want);
         H.arena_cap = want;
     }
     // exact-sum digits absorb 2^31 rows between carry normalisations

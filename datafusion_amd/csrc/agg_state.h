@@ -15,77 +15,6 @@
 namespace dfmi {
 namespace agg {
 
-// Pinned host memory that keeps its capacity (a finish's copies land here by
-// DMA; no zero-fill, no page faults once warm).
-template <typename T>
-struct HostBuf {
-    T* p = nullptr;
-    size_t n = 0, cap = 0;
-    HostBuf() = default;
-    HostBuf(const HostBuf&) = delete;
-    HostBuf& operator=(const HostBuf&) = delete;
-    ~HostBuf() {
-        if (p) (void)hipHostFree(p);
-    }
-    void resize(size_t want) {
-        if (want > cap) {
-            if (p) (void)hipHostFree(p);
-            p = nullptr;
-            cap = 0;
-            const size_t c = std::max<size_t>(want + want / 4, 16);
-            HIP_TRY(hipHostMalloc((void**)&p, c * sizeof(T), hipHostMallocDefault));
-            cap = c;
-        }
-        n = want;
-    }
-    T* data() { return p; }
-    const T* data() const { return p; }
-    size_t size() const { return n; }
-    T& operator[](size_t i) { return p[i]; }
-    const T& operator[](size_t i) const { return p[i]; }
-};
-
-// Device memory with one owner (move-only; freed with it).
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;  // bytes
-    DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        std::swap(p, o.p);
-        std::swap(cap, o.cap);
-        return *this;
-    }
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    template <typename T>
-    T* as() const { return (T*)p; }
-    // A block of exactly `bytes` (the old one freed first, its contents dropped).
-    void alloc(size_t bytes) {
-        if (p) HIP_TRY(hipFree(p));
-        p = nullptr;
-        cap = 0;
-        HIP_TRY(hipMalloc(&p, bytes));
-        cap = bytes;
-    }
-    // At least `bytes` (64 at the least): a scratch buffer that keeps its
-    // capacity and grows with 25 % slack, contents dropped.
-    void* reserve(size_t bytes) {
-        bytes = std::max<size_t>(bytes, 64);
-        if (cap < bytes) alloc(bytes + bytes / 4);
-        return p;
-    }
-    // A block of `want` bytes with the first `keep` bytes copied over.
-    void regrow(dfmi_context* ctx, size_t keep, size_t want) {
-        DevBuf q;
-        q.alloc(want);
-        if (keep) HIP_TRY(hipMemcpyAsync(q.p, p, keep, hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        *this = std::move(q);  // (the old block goes with q)
-    }
-};
-
 // The device hash table of a grouped state (groupby.h; kernels in groupby.hip).
 struct HashDev {
     // The scratch buffers, one slot per use: no two uses that are live at the
@@ -152,7 +81,7 @@ struct FlatGroups {
 struct dfmi_agg_state {
     int device = 0;
     std::vector<const dfmi_aggregate*> aggs;
-    dfmi::agg::DevBuf acc;  // uint64 [kAggCopies][n][kAggWords]; grouped: [kAggCopies][gslots][n + 1][kAggWords]
+    dfmi::DevBuf acc;  // uint64 [kAggCopies][n][kAggWords]; grouped: [kAggCopies][gslots][n + 1][kAggWords]
     size_t acc_words = 0;
     bool failed = false;      // a batch raised an error: the query has failed
     dfmi_error failure{};
@@ -178,8 +107,8 @@ struct dfmi_agg_state {
     dfmi_aggregate* mm[2] = {nullptr, nullptr};
     dfmi_agg_state* mm_state = nullptr;
     // dfmi_aggregate_host_batches: the call's packed input columns, pinned and on the device
-    dfmi::agg::HostBuf<uint8_t> stage_host;
-    dfmi::agg::DevBuf stage_dev;
+    dfmi::HostBuf<uint8_t> stage_host;
+    dfmi::DevBuf stage_dev;
 };
 
 namespace dfmi {

@@ -109,7 +109,7 @@ void build_agg_plan(const dfmi_agg_state* st, const dfmi_program* pred, const df
                 bool have = false;
                 for (int c : X.utf8_cols) have |= c == nd.col;
                 if (!have) X.utf8_cols.push_back(nd.col);
-            } else if (jit::type_width(nd.type) || nd.type == DFMI_TYPE_BOOLEAN) {
+            } else if (dfmi::type_width(nd.type) || nd.type == DFMI_TYPE_BOOLEAN) {
                 reg_num(nd.col, phase);
             }
         }
@@ -529,14 +529,14 @@ extern "C" int32_t dfmi_aggregate_batch(dfmi_context* ctx, dfmi_agg_state* st, c
             count_query_launch();
             ws_commit(ctx, ws);
             HIP_TRY(hipEventRecord(ctx->ev1, stream));
-            HIP_TRY(hipMemcpyAsync(ctx->host_hdr, ws.hdr, kHdrAlloc, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(ctx->host_hdr.p, ws.hdr, kHdrAlloc, hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipEventRecord(ctx->ev2, stream));
             HIP_TRY(hipStreamSynchronize(stream));
             uint64_t ew;
-            memcpy(&ew, ctx->host_hdr + kHdrErr, 8);
+            memcpy(&ew, ctx->host_hdr.p + kHdrErr, 8);
             if (pred && !st->grouped) {  // the kernel's count of selected rows in every 64th block
                 uint64_t sel;
-                memcpy(&sel, ctx->host_hdr + kHdrTotals, 8);
+                memcpy(&sel, ctx->host_hdr.p + kHdrTotals, 8);
                 const int64_t tile_rows = (int64_t)X.BLOCK * X.K * X.M;
                 int64_t sampled = 0;
                 for (int64_t b = 0; b < B.n_tiles; b += 64) sampled += std::min(tile_rows, n - b * tile_rows);

@@ -1,5 +1,5 @@
 // How a caller of the coalesced-batches launch (exec.cpp) stages its small
-// per-call data: the host-batches entry point (host_batch.cpp) moves its
+// per-call data: the host-batches entry point (host_batches.cpp) moves its
 // packed inputs and the batch table with ONE H2D copy (none for small calls,
 // whose kernel reads them from pinned memory), and the outputs with the
 // per-batch headers with ONE D2H copy; the headers are zeroed by the

@@ -40,18 +40,11 @@
 
 #include "../../include/dfmi.h"
 #include "../../include/dfmi_datasource.h"
+#include "col_layout.h"
 
 namespace {
 
-int width_of(int t) {
-    switch (t) {
-        case DFMI_TYPE_INT8: case DFMI_TYPE_UINT8: return 1;
-        case DFMI_TYPE_INT16: case DFMI_TYPE_UINT16: return 2;
-        case DFMI_TYPE_INT32: case DFMI_TYPE_UINT32: case DFMI_TYPE_FLOAT32: return 4;
-        case DFMI_TYPE_INT64: case DFMI_TYPE_UINT64: case DFMI_TYPE_FLOAT64: return 8;
-        default: return 0;
-    }
-}
+using dfmi::type_width;
 
 void set_err(dfmi_error* err, int32_t code, const std::string& m) {
     if (!err) return;
@@ -456,7 +449,7 @@ struct dfmi_csv_reader {
             ColBufs& B = S.cols[c];
             bool ok = B.validity.reserve(bm);
             if (t == DFMI_TYPE_UTF8) ok = ok && B.offsets.reserve((size_t)(n + 1) * 4);
-            else ok = ok && B.values.reserve(t == DFMI_TYPE_BOOLEAN ? bm : (size_t)n * width_of(t));
+            else ok = ok && B.values.reserve(t == DFMI_TYPE_BOOLEAN ? bm : (size_t)n * type_width(t));
             if (!ok) {
                 S.code = DFMI_ERR_DEVICE;
                 S.msg = "hipHostMalloc failed for a CSV batch";
@@ -501,7 +494,7 @@ struct dfmi_csv_reader {
                     if (ty == DFMI_TYPE_BOOLEAN && (r & 63) == 0) ((uint64_t*)B.values.p)[w] = 0;
                     const bool empty = !f[c].present || f[c].e == f[c].b;
                     if (empty) {  // null
-                        if (ty != DFMI_TYPE_BOOLEAN) memset(B.values.p + (size_t)r * width_of(ty), 0, width_of(ty));
+                        if (ty != DFMI_TYPE_BOOLEAN) memset(B.values.p + (size_t)r * type_width(ty), 0, type_width(ty));
                         ++nulls[(size_t)t * nc + c];
                         continue;
                     }
@@ -529,7 +522,7 @@ struct dfmi_csv_reader {
                         memcpy(B.values.p + (size_t)r * 4, &x, 4);
                     } else {
                         const bool sg = ty >= DFMI_TYPE_INT8 && ty <= DFMI_TYPE_INT64;
-                        const int wdt = width_of(ty);
+                        const int wdt = type_width(ty);
                         int64_t v = 0;
                         ok = parse_int(fb, fe, sg, 8 * wdt, &v);
                         memcpy(B.values.p + (size_t)r * wdt, &v, wdt);  // little-endian low bytes
@@ -645,7 +638,7 @@ extern "C" int32_t dfmi_csv_open(const char* path, const dfmi_schema* schema, in
     dfmi_csv_reader* R = new dfmi_csv_reader();
     for (int i = 0; i < schema->num_fields; ++i) {
         const int t = schema->fields[i].type;
-        if (t != DFMI_TYPE_UTF8 && t != DFMI_TYPE_BOOLEAN && !width_of(t)) {
+        if (t != DFMI_TYPE_UTF8 && t != DFMI_TYPE_BOOLEAN && !type_width(t)) {
             delete R;
             set_err(err, DFMI_ERR_NOT_IMPLEMENTED, "CSV column type");
             return DFMI_ERR_NOT_IMPLEMENTED;

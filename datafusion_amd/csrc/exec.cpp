@@ -211,7 +211,7 @@ void build_plan_impl(const dfmi_program* pred, const dfmi_program* const* projs,
         for (const IrNode& nd : p->ir) {
             if (nd.kind != IR_COL) continue;
             if (nd.type == DFMI_TYPE_UTF8) reg_utf8(nd.col);
-            else if (jit::type_width(nd.type) || nd.type == DFMI_TYPE_BOOLEAN) reg_num(nd.col, phase);
+            else if (dfmi::type_width(nd.type) || nd.type == DFMI_TYPE_BOOLEAN) reg_num(nd.col, phase);
         }
     };
     if (pred) reg_prog(pred, X.pred_slots);
@@ -414,7 +414,7 @@ extern "C" int32_t dfmi_context_create(int32_t device, void* stream, dfmi_contex
         c->device = device;
         c->stream = (hipStream_t)stream;
         if (const char* e = getenv("DFMI_SHARED")) c->shared = atoi(e) != 0;
-        HIP_TRY(hipHostMalloc((void**)&c->host_hdr, kHdrAlloc, hipHostMallocDefault));
+        c->host_hdr.resize(kHdrAlloc, dfmi::kGrowExact);
 
         HIP_TRY(hipEventCreate(&c->ev0));
         HIP_TRY(hipEventCreate(&c->ev1));
@@ -427,11 +427,6 @@ extern "C" int32_t dfmi_context_create(int32_t device, void* stream, dfmi_contex
 }
 
 namespace dfmi {
-int ctx_device(const dfmi_context* c) { return c->device; }
-hipStream_t ctx_stream(const dfmi_context* c) { return c->stream; }
-void*& ctx_host_arena(dfmi_context* c) { return c->host_arena; }
-uint64_t& ctx_last_err_key(dfmi_context* c) { return c->last_err_key; }
-void host_arena_release(dfmi_context* c);
 void sort_scratch_release(dfmi_context* c);
 }  // namespace dfmi
 
@@ -440,15 +435,6 @@ extern "C" void dfmi_context_destroy(dfmi_context* c) {
     (void)hipSetDevice(c->device);
     dfmi::host_arena_release(c);
     dfmi::sort_scratch_release(c);
-    if (c->ws) (void)hipFree(c->ws);
-    if (c->scratch) (void)hipFree(c->scratch);
-    if (c->utf8_src) (void)hipFree(c->utf8_src);
-    if (c->host_hdr) (void)hipHostFree(c->host_hdr);
-    if (c->bmeta) (void)hipFree(c->bmeta);
-    if (c->bhdr) (void)hipFree(c->bhdr);
-    if (c->ones) (void)hipFree(c->ones);
-    if (c->host_bmeta) (void)hipHostFree(c->host_bmeta);
-    if (c->host_bhdr) (void)hipHostFree(c->host_bhdr);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -583,10 +569,10 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
             }
             const size_t row_bytes = (size_t)((n + 63) & ~63ll);
             if (!bool_out.empty() || !valid_out.empty())
-                ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, (bool_out.size() + valid_out.size()) * row_bytes);
+                ctx->scratch.reserve((bool_out.size() + valid_out.size()) * row_bytes, kCtxDev);
             const bool two_pass = pred && X.gather == 3 && !X.utf8_outs.empty();
             const size_t src_bytes = ((size_t)n * 4 + 255) & ~(size_t)255;  // one i32 source start per row
-            if (two_pass) ensure(ctx, &ctx->utf8_src, &ctx->utf8_src_bytes, X.utf8_outs.size() * src_bytes);
+            if (two_pass) ctx->utf8_src.reserve(X.utf8_outs.size() * src_bytes, kCtxDev);
             A.n_rows = n;
             A.n_tiles = (int)n_tiles;
             bind_inputs(A, X, in);
@@ -600,13 +586,13 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
             }
             if (two_pass)
                 for (size_t j = 0; j < X.utf8_outs.size(); ++j)
-                    A.out_src[X.utf8_outs[j].first] = (int*)(ctx->utf8_src + j * src_bytes);
+                    A.out_src[X.utf8_outs[j].first] = (int*)(ctx->utf8_src.as<uint8_t>() + j * src_bytes);
             for (size_t i = 0; i < bool_out.size(); ++i) {
                 bool_dst[bool_out[i]] = (uint8_t*)outs[bool_out[i]].values;
-                A.out[bool_out[i]] = ctx->scratch + i * row_bytes;
+                A.out[bool_out[i]] = ctx->scratch.as<uint8_t>() + i * row_bytes;
             }
             for (size_t i = 0; i < valid_out.size(); ++i)
-                A.out_valid[valid_out[i]] = ctx->scratch + (bool_out.size() + i) * row_bytes;
+                A.out_valid[valid_out[i]] = ctx->scratch.as<uint8_t>() + (bool_out.size() + i) * row_bytes;
             bind_literals(A, X);
             // A look-back that made no progress for 2 s (ERRK_LOOKBACK_TIMEOUT:
             // e.g. the GPU time-sliced away from this queue for that long) is
@@ -639,24 +625,24 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
                 if (prof) ph[2] += tms(t_c, t_d);
                 auto t_e = tnow();
                 if (prof) ph[3] += tms(t_d, t_e);
-                HIP_TRY(hipMemcpyAsync(ctx->host_hdr, ws.hdr, kHdrAlloc, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(ctx->host_hdr.p, ws.hdr, kHdrAlloc, hipMemcpyDeviceToHost, st));
                 if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev2, st));
                 HIP_TRY(hipStreamSynchronize(st));
                 auto t_f = tnow();
                 if (prof) ph[4] += tms(t_e, t_f);
                 uint64_t ew;
-                memcpy(&ew, ctx->host_hdr + kHdrErr, 8);
+                memcpy(&ew, ctx->host_hdr.p + kHdrErr, 8);
                 decode_err_word(ew, dev_key, dev_kind);
                 if (A.mode & 32) {
                     uint64_t g5[5];
-                    memcpy(g5, ctx->host_hdr + kHdrStats + 64, sizeof g5);
+                    memcpy(g5, ctx->host_hdr.p + kHdrStats + 64, sizeof g5);
                     fprintf(stderr, "dfmi utf8 gather cycles (summed over waves): staging %llu setup %llu zero %llu place %llu "
                             "store %llu\n", (unsigned long long)g5[0], (unsigned long long)g5[1], (unsigned long long)g5[2],
                             (unsigned long long)g5[3], (unsigned long long)g5[4]);
                 }
                 if (A.mode & 4) {
                     uint64_t st3[3];
-                    memcpy(st3, ctx->host_hdr + kHdrStats, sizeof st3);
+                    memcpy(st3, ctx->host_hdr.p + kHdrStats, sizeof st3);
                     fprintf(stderr, "dfmi look-back: tiles %lld polls %llu sleeps %llu wait %.3f ms (summed over tiles)\n",
                             (long long)n_tiles, (unsigned long long)st3[0], (unsigned long long)st3[1], st3[2] * 1e-5);
                 }
@@ -711,7 +697,7 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
         // ---- results
         uint64_t totals[24];
         memset(totals, 0, sizeof totals);
-        if (launch) memcpy(totals, ctx->host_hdr + kHdrTotals, sizeof totals);
+        if (launch) memcpy(totals, ctx->host_hdr.p + kHdrTotals, sizeof totals);
         const int64_t out_rows = pred ? (int64_t)totals[0] : n;
         if (hint_key && launch) {  // what this shape selected, for its next large batch
             if (ctx->sel_hint.size() >= 4096) ctx->sel_hint.clear();
@@ -880,14 +866,12 @@ int32_t dfmi::filter_project_batches_staged(dfmi_context* ctx, const dfmi_progra
         ctx->last_kernel = X.kname;
         prof.mark(1);
         if (!staged) {
-            ensure_host(&ctx->host_bmeta, &ctx->host_bmeta_bytes, meta_bytes);
-            ensure(ctx, &ctx->bmeta, &ctx->bmeta_bytes, meta_bytes);
-            ensure_host(&ctx->host_bhdr, &ctx->host_bhdr_bytes, (size_t)nb * kBHdr);
-            ensure(ctx, &ctx->bhdr, &ctx->bhdr_bytes, (size_t)nb * kBHdr);
-            host_meta = ctx->host_bmeta;
-            dev_meta = ctx->bmeta;
-            dev_hdr = ctx->bhdr;
-            host_hdr = ctx->host_bhdr;
+            ctx->host_bmeta.resize(meta_bytes, kCtxPinned);
+            ctx->host_bhdr.resize((size_t)nb * kBHdr, kCtxPinned);
+            host_meta = ctx->host_bmeta.p;
+            dev_meta = (uint8_t*)ctx->bmeta.reserve(meta_bytes, kCtxDev);
+            dev_hdr = (uint8_t*)ctx->bhdr.reserve((size_t)nb * kBHdr, kCtxDev);
+            host_hdr = ctx->host_bhdr.p;
         }
         bool need_ones = false;
         for (int i = 0; i < ncols && !need_ones; ++i)
@@ -896,16 +880,16 @@ int32_t dfmi::filter_project_batches_staged(dfmi_context* ctx, const dfmi_progra
                     if (!(ins[b].columns[i].validity && ins[b].columns[i].null_count > 0)) need_ones = true;
         if (need_ones) {
             const size_t nbm = (size_t)((maxn + 63) / 64 * 8 + 64);
-            if (ctx->ones_bytes < nbm) {
-                ensure(ctx, &ctx->ones, &ctx->ones_bytes, nbm);
-                HIP_TRY(hipMemsetAsync(ctx->ones, 0xff, ctx->ones_bytes, st));
+            if (ctx->ones.cap < nbm) {
+                ctx->ones.reserve(nbm, kCtxDev);
+                HIP_TRY(hipMemsetAsync(ctx->ones.p, 0xff, ctx->ones.cap, st));
             }
         }
         uint64_t* tab = (uint64_t*)host_meta;
         int32_t* tile_batch = (int32_t*)(host_meta + table_bytes);
         auto valid_of = [&](const dfmi_column& c, int col) -> uint64_t {
             if (!nullable[col]) return 0;
-            return (uint64_t)((c.validity && c.null_count > 0) ? c.validity : ctx->ones);
+            return (uint64_t)((c.validity && c.null_count > 0) ? c.validity : ctx->ones.p);
         };
         for (int32_t b = 0; b < nb; ++b) {
             const dfmi_batch& in = ins[b];
@@ -919,7 +903,7 @@ int32_t dfmi::filter_project_batches_staged(dfmi_context* ctx, const dfmi_progra
             row[3] = (uint64_t)(dev_hdr + (size_t)b * kBHdr + 24 * 8);
             for (size_t sl = 0; sl < X.num_cols.size(); ++sl) {
                 const dfmi_column& c = in.columns[X.num_cols[sl]];
-                const int w = jit::type_width(c.type);
+                const int w = dfmi::type_width(c.type);
                 if (in.num_rows > 0 && !c.values) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "column values pointer is NULL"};
                 if (w && ((uintptr_t)c.values & (w - 1)))
                     throw Fail{DFMI_ERR_INVALID_ARGUMENT, "column values must be aligned to their width"};
@@ -991,7 +975,7 @@ int32_t dfmi::filter_project_batches_staged(dfmi_context* ctx, const dfmi_progra
                 if (stage && stage->cleared) *stage->cleared = true;
                 if (X.hdr_out && stage->hdr_written) *stage->hdr_written = true;
                 if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev1, st));
-                if (!staged) HIP_TRY(hipMemcpyAsync(ctx->host_bhdr, ctx->bhdr, (size_t)nb * kBHdr, hipMemcpyDeviceToHost, st));
+                if (!staged) HIP_TRY(hipMemcpyAsync(ctx->host_bhdr.p, ctx->bhdr.p, (size_t)nb * kBHdr, hipMemcpyDeviceToHost, st));
             }
             for (int32_t b = 0; b < nb; ++b)  // empty batches: Utf8 offsets = [0]
                 if (ins[b].num_rows == 0)

@@ -9,8 +9,15 @@
 #include <string>
 #include <unordered_map>
 
+#include "buffers.h"
+#include "col_layout.h"
 #include "dfmi_program.h"
 #include "jit.h"
+
+namespace dfmi {
+struct Arena;  // host_arena.h
+void host_arena_release(dfmi_context* c);  // host_chunks.cpp
+}  // namespace dfmi
 
 // Workspace header layout (device, zero when a launch starts).
 static constexpr size_t kHdrTicket = 0;
@@ -31,23 +38,20 @@ struct dfmi_context {
     // its own status size (a 1024-row call after a 1e9-row call must not
     // zero 31 MB from one block); a larger leftover is cleared by memset of
     // just the prefix a later launch needs (ws_acquire).
-    uint8_t* ws = nullptr;
-    size_t ws_bytes = 0;
+    dfmi::DevBuf ws;
     size_t status_cap = 0;       // bytes per status buffer
     int parity = 0;              // pair the next launch uses
     size_t dirty_lo[2] = {0, 0}, dirty_hi[2] = {0, 0};
     bool ws_valid = false;       // the invariant above holds (else re-zero everything)
-    uint8_t* scratch = nullptr;  // Boolean output bytes (filtered)
-    size_t scratch_bytes = 0;
-    uint8_t* utf8_src = nullptr;  // two-pass Utf8 gather: source start per selected row
-    size_t utf8_src_bytes = 0;
-    uint8_t* host_hdr = nullptr; // pinned copy of the header
+    dfmi::DevBuf scratch;   // Boolean output bytes (filtered)
+    dfmi::DevBuf utf8_src;  // two-pass Utf8 gather: source start per selected row
+    dfmi::HostBuf<uint8_t> host_hdr;  // pinned copy of the header
     bool timing = true;  // record HIP events around launches (dfmi_context_set_timing)
     // the GPU is shared with other processes (dfmi_context_set_shared, or
     // DFMI_SHARED=1 at creation): look-back kernels take their tiles in
     // ticket order from the first launch instead of after a 2 s timeout
     bool shared = false;
-    void* host_arena = nullptr;  // host_batch.cpp's staging arena (per context: no shared state)
+    dfmi::Arena* host_arena = nullptr;  // the host paths' staging arena (host_arena.h; per context: no shared state)
     void* sort_scratch = nullptr;  // sort.cpp's device scratch, kept across dfmi_sort_batches calls
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     double last_total_ms = 0, last_main_ms = 0, last_compile_ms = 0;
@@ -60,16 +64,8 @@ struct dfmi_context {
     // coalesced batches (dfmi_filter_project_batches): per-call batch table
     // and per-batch headers, device + pinned host mirrors; an all-valid
     // bitmap for batches without validity in a column others have it for
-    uint8_t* bmeta = nullptr;
-    size_t bmeta_bytes = 0;
-    uint8_t* host_bmeta = nullptr;
-    size_t host_bmeta_bytes = 0;
-    uint8_t* bhdr = nullptr;
-    size_t bhdr_bytes = 0;
-    uint8_t* host_bhdr = nullptr;
-    size_t host_bhdr_bytes = 0;
-    uint8_t* ones = nullptr;
-    size_t ones_bytes = 0;
+    dfmi::DevBuf bmeta, bhdr, ones;
+    dfmi::HostBuf<uint8_t> host_bmeta, host_bhdr;
     // selectivity of each query shape's last large batch (exec.cpp
     // kSubtileMinRows): picks the sub-tile kernel for low selectivity
     std::unordered_map<uint64_t, double> sel_hint;
@@ -81,12 +77,7 @@ struct dfmi_context {
 namespace dfmi {
 namespace xi {
 
-// (set_err and the entry points' error frame: abi_guard.h, through jit.h)
-#define HIP_TRY(x)                                                                        \
-    do {                                                                                   \
-        hipError_t e_ = (x);                                                               \
-        if (e_ != hipSuccess) throw Fail{DFMI_ERR_DEVICE, std::string(#x ": ") + hipGetErrorString(e_)}; \
-    } while (0)
+// (set_err and the entry points' error frame: abi_guard.h; HIP_TRY: buffers.h)
 
 inline bool gatherable(int t, uint32_t flags) {
     if (t == DFMI_TYPE_FLOAT64 || t == DFMI_TYPE_UTF8) return true;  // filter.rs:84,94
@@ -111,25 +102,8 @@ struct Err {
     }
 };
 
-inline void ensure_host(uint8_t** buf, size_t* have, size_t need) {  // pinned
-    if (*have >= need) return;
-    if (*buf) HIP_TRY(hipHostFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    size_t cap = std::max(need, (size_t)1 << 16);
-    HIP_TRY(hipHostMalloc((void**)buf, cap, hipHostMallocDefault));
-    *have = cap;
-}
-
-inline void ensure(dfmi_context* ctx, uint8_t** buf, size_t* have, size_t need) {
-    if (*have >= need) return;
-    if (*buf) HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    size_t cap = std::max(need, (size_t)1 << 20);
-    HIP_TRY(hipMalloc(buf, cap));
-    *have = cap;
-}
+// The context's buffers grow to what a call needs, with a floor and no slack.
+constexpr Grow kCtxDev{(size_t)1 << 20, 0}, kCtxPinned{(size_t)1 << 16, 0};
 
 // One launch's share of the double-buffered workspace (see dfmi_context):
 // its header and status buffer (zero on entry) and what its blocks clear for
@@ -145,14 +119,15 @@ struct WsLease {
 };
 
 inline WsLease ws_acquire(dfmi_context* ctx, size_t status_bytes, hipStream_t st) {
-    if (!ctx->ws || status_bytes > ctx->status_cap) {
+    uint8_t* ws = ctx->ws.as<uint8_t>();
+    if (!ws || status_bytes > ctx->status_cap) {
         const size_t cap = (std::max(status_bytes, (size_t)1 << 20) + 255) & ~(size_t)255;
-        ensure(ctx, &ctx->ws, &ctx->ws_bytes, 2 * kHdrAlloc + 2 * cap);
+        ws = (uint8_t*)ctx->ws.reserve(2 * kHdrAlloc + 2 * cap, kCtxDev);
         ctx->status_cap = cap;
         ctx->ws_valid = false;
     }
     if (!ctx->ws_valid) {  // first use, growth, or an interrupted call
-        HIP_TRY(hipMemsetAsync(ctx->ws, 0, 2 * kHdrAlloc + 2 * ctx->status_cap, st));
+        HIP_TRY(hipMemsetAsync(ws, 0, 2 * kHdrAlloc + 2 * ctx->status_cap, st));
         ctx->dirty_lo[0] = ctx->dirty_lo[1] = ctx->dirty_hi[0] = ctx->dirty_hi[1] = 0;
         ctx->ws_valid = true;
     }
@@ -160,8 +135,8 @@ inline WsLease ws_acquire(dfmi_context* ctx, size_t status_bytes, hipStream_t st
     const int p = ctx->parity, q = 1 - p;
     l.par = p;
     l.status_bytes = status_bytes;
-    l.hdr = ctx->ws + p * kHdrAlloc;
-    l.status = ctx->ws + 2 * kHdrAlloc + p * ctx->status_cap;
+    l.hdr = ws + p * kHdrAlloc;
+    l.status = ws + 2 * kHdrAlloc + p * ctx->status_cap;
     // the prefix this launch needs must be zero: what is left dirty in this
     // pair is cleared whole, by one memset (so a small launch after a large
     // one pays it once, not on every later use of the pair)
@@ -175,7 +150,7 @@ inline WsLease ws_acquire(dfmi_context* ctx, size_t status_bytes, hipStream_t st
     // a larger leftover (a full-table launch before a 1024-row one) is
     // cleared here once, by one memset, and later launches are back to
     // clearing in the kernel
-    uint8_t* other = ctx->ws + 2 * kHdrAlloc + q * ctx->status_cap;
+    uint8_t* other = ws + 2 * kHdrAlloc + q * ctx->status_cap;
     size_t& qlo = ctx->dirty_lo[q];
     size_t& qhi = ctx->dirty_hi[q];
     if (qhi > qlo && qhi - qlo > std::max<size_t>(4 * status_bytes, (size_t)64 << 10)) {
@@ -190,7 +165,7 @@ inline WsLease ws_acquire(dfmi_context* ctx, size_t status_bytes, hipStream_t st
         l.clear_status = other;
         l.clear_words = 0;
     }
-    l.clear_hdr = ctx->ws + q * kHdrAlloc;
+    l.clear_hdr = ws + q * kHdrAlloc;
     ctx->ws_valid = false;  // until the launch is enqueued (ws_commit)
     return l;
 }

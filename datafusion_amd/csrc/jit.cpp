@@ -82,16 +82,6 @@ struct Val {
 
 }  // namespace
 
-int type_width(int t) {
-    switch (t) {
-        case DFMI_TYPE_INT8: case DFMI_TYPE_UINT8: return 1;
-        case DFMI_TYPE_INT16: case DFMI_TYPE_UINT16: return 2;
-        case DFMI_TYPE_INT32: case DFMI_TYPE_UINT32: case DFMI_TYPE_FLOAT32: return 4;
-        case DFMI_TYPE_INT64: case DFMI_TYPE_UINT64: case DFMI_TYPE_FLOAT64: return 8;
-        default: return 0;
-    }
-}
-
 bool may_introduce_nulls(const dfmi_program* p) {
     for (const IrNode& n : p->ir)
         if (n.kind == IR_CAST && !cast_total(p->ir[n.l].type, n.type)) return true;

@@ -9,6 +9,7 @@
 
 #include "../../include/dfmi.h"
 #include "abi_guard.h"
+#include "col_layout.h"
 #include "dfmi_program.h"
 
 namespace dfmi {
@@ -59,7 +60,7 @@ struct Launch {
     // (64 cost ~9% of the C2 kernel in polling traffic)
     int window = 8;
     int late_proj = 0;  // projection-only columns loaded after the look-back (byte-light predicates)
-    // coalesced batches of one tile each (host_batch.cpp small calls): every
+    // coalesced batches of one tile each (host_batches.cpp small calls): every
     // block copies its batch's finished header to Args::hdr_out and zeroes it
     int hdr_out = 0;
     // tiles taken from an atomic ticket in the order blocks start instead of
@@ -158,9 +159,8 @@ inline int batch_slot_out(const Launch& X, int o) {
 }
 inline int batch_words(const Launch& X, int nout) { return batch_slot_out(X, nout); }
 
-// Bytes per value of a fixed-width dfmi_type (0 otherwise) and the C++ type
-// the generated code holds it in (i8 .. u64, float, double).
-int type_width(int t);
+// The C++ type the generated code holds a fixed-width dfmi_type in (i8 ..
+// u64, float, double; its bytes: col_layout.h type_width).
 const char* ctype(int t);
 
 // True when evaluating p over a batch without nulls can still produce a null

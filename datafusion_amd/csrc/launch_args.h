@@ -17,7 +17,7 @@ inline void bind_inputs(Args& A, const jit::Launch& X, const dfmi_batch* in) {
     for (size_t s = 0; s < X.num_cols.size(); ++s) {
         const dfmi_column& c = in->columns[X.num_cols[s]];
         if (!c.values) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "column values pointer is NULL"};
-        const int w = jit::type_width(c.type);
+        const int w = dfmi::type_width(c.type);
         if (w && ((uintptr_t)c.values & (w - 1)))
             throw Fail{DFMI_ERR_INVALID_ARGUMENT, "column values must be aligned to their width"};
         A.col[s] = c.values;

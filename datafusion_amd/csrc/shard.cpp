@@ -420,7 +420,7 @@ extern "C" int32_t dfmi_shard_gather_to_root(dfmi_context* ctx, dfmi_shard_comm*
             }
             for (int o = 0; o < nout; ++o) {
                 const int t = local[o].type;
-                const int w = jit::type_width(t);
+                const int w = dfmi::type_width(t);
                 const bool has_nulls = nulls_of(o) > 0;
                 int64_t row0 = 0, b0 = 0;
                 for (int r = 0; r < world; ++r) {

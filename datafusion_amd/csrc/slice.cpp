@@ -25,16 +25,6 @@ namespace dfmi {
 hipError_t launch_shift_bits(const uint8_t* src, long long bit0, long long nbits, uint8_t* dst, hipStream_t st);
 
 namespace {
-int width(int t) {
-    switch (t) {
-        case DFMI_TYPE_INT8: case DFMI_TYPE_UINT8: return 1;
-        case DFMI_TYPE_INT16: case DFMI_TYPE_UINT16: return 2;
-        case DFMI_TYPE_INT32: case DFMI_TYPE_UINT32: case DFMI_TYPE_FLOAT32: return 4;
-        case DFMI_TYPE_INT64: case DFMI_TYPE_UINT64: case DFMI_TYPE_FLOAT64: return 8;
-        default: return 0;
-    }
-}
-
 void host_shift(const uint8_t* src, int64_t bit0, int64_t nbits, uint8_t* dst) {
     const int64_t nw = (nbits + 63) / 64, src_bytes = (bit0 + nbits + 7) / 8;
     for (int64_t i = 0; i < nw; ++i) {
@@ -98,7 +88,7 @@ const dfmi_batch* unslice(const dfmi_batch* ins, int32_t nb, Unsliced& u, bool d
                 } else if (c.type == DFMI_TYPE_BOOLEAN) {
                     c.values = bitmap((const uint8_t*)c.values, off, c.length);
                 } else if (c.values) {
-                    c.values = (const uint8_t*)c.values + off * width(c.type);
+                    c.values = (const uint8_t*)c.values + off * type_width(c.type);
                 }
                 c.offset = 0;
             }

@@ -15,9 +15,6 @@ namespace dfmi {
 namespace srt {
 namespace {
 
-using agg::DevBuf;
-using agg::HostBuf;
-
 // Select switch point (DESIGN.md §6 "ORDER BY"): the radix select runs when
 // the input has at least kSelectMinRows rows and LIMIT keeps at most one row
 // in kSelectRatio.
@@ -73,16 +70,6 @@ struct PhaseClock {
 Scratch& scratch(dfmi_context* ctx) {
     if (!ctx->sort_scratch) ctx->sort_scratch = new Scratch();
     return *(Scratch*)ctx->sort_scratch;
-}
-
-int type_width(int t) {  // value bytes of a fixed-width type (0: Boolean / Utf8)
-    switch (t) {
-        case DFMI_TYPE_INT8: case DFMI_TYPE_UINT8: return 1;
-        case DFMI_TYPE_INT16: case DFMI_TYPE_UINT16: return 2;
-        case DFMI_TYPE_INT32: case DFMI_TYPE_UINT32: case DFMI_TYPE_FLOAT32: return 4;
-        case DFMI_TYPE_INT64: case DFMI_TYPE_UINT64: case DFMI_TYPE_FLOAT64: return 8;
-        default: return 0;
-    }
 }
 
 int bit_length(unsigned long long v) {

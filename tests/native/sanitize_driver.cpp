@@ -2,13 +2,16 @@
 // front ends -- the expression compiler (csrc/compile.cpp) and the CSV
 // reader (csrc/csv_reader.cpp) and the aggregate extension's host-only part
 // (csrc/agg_host.cpp: exact-sum arithmetic, the host group map, the partials
-// that ranks exchange) -- plus the CPU oracle, built with
+// that ranks exchange) and the host paths' device-free parts (bitmap
+// splicing, the worker pool, the chunk and host-batches layouts:
+// csrc/host_bits.h, host_pool.h, host_plan.cpp) -- plus the CPU oracle, built with
 // AddressSanitizer + UndefinedBehaviorSanitizer and driven over random
 // expressions, random batches, generated CSV files (quotes, CRLF, empty
 // and missing fields, bad numbers), random aggregates merged from serialised
 // partials and compared bit for bit with the oracle, and malformed partials.
 // Exit 0 = no finding; the sanitizers abort on the first one. Built and run
 // by tests/test_sanitize_cpu.py.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -16,9 +19,14 @@
 #include <cstring>
 #include <random>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../datafusion_amd/csrc/agg_host.h"
+#include "../../datafusion_amd/csrc/col_layout.h"
+#include "../../datafusion_amd/csrc/host_bits.h"
+#include "../../datafusion_amd/csrc/host_plan.h"
+#include "../../datafusion_amd/csrc/host_pool.h"
 #include "../../include/dfmi.h"
 #include "../../include/dfmi_datasource.h"
 #include "../../oracle/oracle.h"
@@ -533,6 +541,283 @@ int check_malformed_partials() {
     return 0;
 }
 
+// ---- the host paths' device-free parts (csrc/host_bits.h, host_pool.h, host_plan.cpp)
+namespace hst = dfmi::host;
+
+constexpr int64_t kBitN[] = {0, 1, 7, 8, 9, 63, 64, 65, 127, 128, 129, 200};
+
+bool bit_at(const uint8_t* b, int64_t i) { return (b[i >> 3] >> (i & 7)) & 1; }
+
+// append_bits / append_ones at every pos in 0..71 and every n of kBitN, into a
+// heap block of exactly ceil((pos + n) / 8) + 8 bytes (the slack append_bits'
+// comment promises) pre-filled with random bits: bits below pos kept, bits
+// [pos, pos + n) the source's (or ones), and after finish_bitmap the rest of
+// the last byte zero -- each against a bit-by-bit loop.
+int check_bitmaps() {
+    long cases = 0;
+    for (int64_t pos = 0; pos <= 71; ++pos)
+        for (int64_t n : kBitN) {
+            const size_t src_bytes = (size_t)(n + 7) / 8, dst_bytes = (size_t)(pos + n + 7) / 8 + 8;
+            std::vector<uint8_t> src(src_bytes), before(dst_bytes);
+            for (uint8_t& b : src) b = (uint8_t)rng();
+            for (uint8_t& b : before) b = (uint8_t)rng();
+            for (int ones = 0; ones < 2; ++ones) {
+                std::vector<uint8_t> dst = before;  // (exactly dst_bytes on the heap: ASan sees a byte past it)
+                if (ones) hst::append_ones(dst.data(), pos, n);
+                else hst::append_bits(dst.data(), pos, src.data(), n);
+                for (int64_t i = 0; i < pos; ++i)
+                    if (bit_at(dst.data(), i) != bit_at(before.data(), i)) return 40;
+                for (int64_t i = 0; i < n; ++i)
+                    if (bit_at(dst.data(), pos + i) != (ones ? true : bit_at(src.data(), i))) return 41;
+                // (bits past pos + n may be overwritten: the next append, or finish_bitmap, owns them)
+                hst::finish_bitmap(dst.data(), pos + n);
+                for (int64_t i = 0; i < pos + n; ++i)
+                    if (bit_at(dst.data(), i) != (i < pos ? bit_at(before.data(), i) : (ones ? true : bit_at(src.data(), i - pos))))
+                        return 43;
+                for (int64_t i = pos + n; i < (pos + n + 7) / 8 * 8; ++i)
+                    if (bit_at(dst.data(), i)) return 44;
+                ++cases;
+            }
+        }
+    printf("bitmaps: %ld append_bits / append_ones / finish_bitmap cases\n", cases);
+    return 0;
+}
+
+// chunk_rows_for: the chunks tile [0, n) exactly, every chunk but the last is
+// a multiple of 512 rows, and a batch up to 1.5 chunks is one chunk.
+int check_chunk_rows() {
+    unsetenv("DFMI_HOST_CHUNK_ROWS");
+    for (int64_t n : {0ll, 1ll, 511ll, 512ll, 513ll, 65536ll, 98304ll, 98305ll, 10000000ll})
+        for (double bpr : {0.125, 24.0, 1000.0}) {
+            const int64_t crows = hst::chunk_rows_for(n, bpr);
+            if (crows < 1) return 50;
+            const std::vector<hst::Chunk> ch = hst::chunks_of(n, crows);
+            if (ch.empty()) return 51;
+            int64_t at = 0;
+            for (size_t k = 0; k < ch.size(); ++k) {
+                if (ch[k].r0 != at || ch[k].rows < 0 || (n > 0 && ch[k].rows == 0)) return 52;
+                if (k + 1 < ch.size() && ch[k].rows % 512) return 53;
+                at += ch[k].rows;
+            }
+            if (at != n) return 54;
+            // the target: 48 MiB of input per chunk, 65536 rows at the least
+            const int64_t target = std::max<int64_t>((int64_t)(48.0 * (1 << 20) / std::max(bpr, 1.0)), 1 << 16);
+            if (n <= target + target / 2 && ch.size() != 1) return 55;
+            if (n > target + target / 2 && ch.size() < 2) return 56;
+        }
+    setenv("DFMI_HOST_CHUNK_ROWS", "512", 1);  // the override: 512-row chunks
+    const std::vector<hst::Chunk> ch = hst::chunks_of(2000, hst::chunk_rows_for(2000, 24.0));
+    unsetenv("DFMI_HOST_CHUNK_ROWS");
+    if (ch.size() != 4 || ch[3].r0 != 1536 || ch[3].rows != 464) return 57;
+    printf("chunk rows: 27 cases tile their batches\n");
+    return 0;
+}
+
+// Half-open byte ranges that must be 256-aligned, disjoint and inside `total`.
+struct Regions {
+    std::vector<std::pair<size_t, size_t>> r;
+    void add(size_t off, size_t bytes) { r.emplace_back(off, off + bytes); }
+    bool ok(size_t total) {
+        std::sort(r.begin(), r.end());
+        for (size_t i = 0; i < r.size(); ++i) {
+            if (r[i].first % 256 || r[i].second > total) return false;
+            if (i && r[i].first < r[i - 1].second) return false;
+        }
+        return true;
+    }
+};
+
+// A batch of Float64, nullable Boolean, Utf8 and Int8 columns (its buffers live in the struct).
+struct PlanBatch {
+    std::vector<double> f;
+    std::vector<uint8_t> bits, valid, data;
+    std::vector<int32_t> offs;
+    std::vector<int8_t> i8;
+    dfmi_column cols[4];
+    dfmi_batch batch;
+    PlanBatch(int64_t n, bool empty_strings) {
+        f.assign((size_t)n, 0.5);
+        bits.assign((size_t)(n + 63) / 64 * 8 + 8, 0x5a);
+        valid.assign(bits.size(), 0xf7);
+        offs.assign((size_t)n + 1, 0);
+        for (int64_t r = 0; r < n && !empty_strings; ++r) offs[(size_t)r + 1] = offs[(size_t)r] + (int32_t)(r % 5);
+        data.assign((size_t)offs[(size_t)n] + 1, 'x');  // (a zero-length data buffer still has an address)
+        i8.assign((size_t)n + 1, 3);
+        memset(cols, 0, sizeof cols);
+        const int types[4] = {DFMI_TYPE_FLOAT64, DFMI_TYPE_BOOLEAN, DFMI_TYPE_UTF8, DFMI_TYPE_INT8};
+        const void* vals[4] = {f.data(), bits.data(), data.data(), i8.data()};
+        for (int c = 0; c < 4; ++c) {
+            cols[c].type = types[c];
+            cols[c].length = n;
+            cols[c].values = vals[c];
+        }
+        if (n == 0) cols[0].values = &cols[0];  // (an empty vector's data() may be null; the pointer is never read)
+        cols[1].validity = valid.data();
+        cols[1].null_count = n ? 1 : 0;
+        cols[2].offsets = offs.data();
+        batch = dfmi_batch{4, 0, n, cols};
+    }
+};
+
+// The fake pin predicate: buffers of at most 200 bytes, and the Int8 column's, count as pinned.
+const void* g_direct_base = nullptr;
+bool fake_pinned(const void* p, size_t n) { return n <= 200 || p == g_direct_base; }
+
+// The chunk pipeline's input / output plans and hb_layout over batches of 0,
+// 1 and 1025 rows with one output of each type: every region 256-aligned,
+// disjoint, inside the totals; staged regions one prefix of staged_bytes.
+int check_plans() {
+    dfmi_field fields[4] = {{"f", DFMI_TYPE_FLOAT64, 0}, {"b", DFMI_TYPE_BOOLEAN, 1}, {"s", DFMI_TYPE_UTF8, 0},
+                            {"i", DFMI_TYPE_INT8, 0}};
+    dfmi_schema schema = {4, 0, fields};
+    const uint32_t flags = DFMI_FLAG_EXT_GATHER_ALL;
+    dfmi_program* pred = nullptr;
+    dfmi_program* projs[4] = {};
+    dfmi_error err;
+    dfmi_expr_node nd[3];
+    memset(nd, 0, sizeof nd);
+    nd[0].kind = DFMI_EXPR_COLUMN, nd[0].column = 0;
+    nd[1].kind = DFMI_EXPR_LITERAL, nd[1].data_type = DFMI_TYPE_FLOAT64, nd[1].f64 = 0.25;
+    nd[2].kind = DFMI_EXPR_BINARY, nd[2].op = DFMI_OP_GT;
+    if (dfmi_compile_scalar_expr(nd, 3, &schema, flags, &pred, &err) != DFMI_OK) return 60;
+    for (int c = 0; c < 4; ++c) {
+        dfmi_expr_node col;
+        memset(&col, 0, sizeof col);
+        col.kind = DFMI_EXPR_COLUMN, col.column = c;
+        if (dfmi_compile_scalar_expr(&col, 1, &schema, flags, &projs[c], &err) != DFMI_OK) return 61;
+    }
+    int plans = 0;
+    for (int64_t n : {0ll, 1ll, 1025ll})
+        for (int empty_strings = 0; empty_strings < 2; ++empty_strings) {
+            PlanBatch B(n, empty_strings != 0);
+            g_direct_base = B.i8.data();
+            const hst::Shape S = hst::call_shape(pred, projs, 4, B.batch);
+            if (S.nout != 4 || S.ncols != 4) return 62;
+            for (int c = 0; c < 4; ++c)
+                if (!S.need[c] || S.otype[c] != B.cols[c].type || S.osrc[c] != c || S.passthrough[c]) return 63;
+            // one chunk, and 512-row chunks
+            for (int64_t crows : {std::max<int64_t>(n, 1), (int64_t)512}) {
+                const std::vector<hst::Chunk> chunks = hst::chunks_of(n, crows);
+                std::vector<hst::InPlan> inplans;
+                for (const hst::Chunk& ch : chunks) {
+                    const hst::InPlan P = hst::plan_chunk_in(B.batch, S.need, ch, fake_pinned);
+                    Regions staged, direct;
+                    size_t staged_end = 0;
+                    for (const hst::Buf& b : P.bufs) {
+                        if (!b.src) continue;  // absent
+                        if (b.direct != (b.bytes && fake_pinned(b.src, b.bytes))) return 64;
+                        (b.direct ? direct : staged).add(b.off, b.bytes + 8);  // (a kernel reads whole words)
+                        if (!b.direct) staged_end = std::max(staged_end, b.off + b.bytes);
+                    }
+                    if (!staged.ok(P.staged_bytes) || staged_end > P.staged_bytes || P.staged_bytes > P.total) return 65;
+                    for (auto& r : direct.r)
+                        if (r.first < P.staged_bytes) return 66;  // the staged ones are one prefix
+                    if (!direct.ok(P.total)) return 67;
+                    // values, validity (column b), offsets (column s) of a needed column are planned
+                    if (!P.bufs[0].src || !P.bufs[3].src || !P.bufs[4].src || !P.bufs[6].src || !P.bufs[8].src || !P.bufs[9].src)
+                        return 68;
+                    if (P.bufs[1].src || P.bufs[2].src || P.bufs[5].src) return 69;
+                    inplans.push_back(P);
+                    ++plans;
+                }
+                const hst::OutRegion O = hst::plan_chunk_out(S, inplans, std::max<int64_t>(crows, 1));
+                Regions out;
+                for (int o = 0; o < 4; ++o) {
+                    const hst::OutPlan& p = O.col[o];
+                    if (S.otype[o] == DFMI_TYPE_UTF8) {
+                        out.add(p.offsets, (size_t)(std::max<int64_t>(crows, 1) + 1) * 4);
+                        out.add(p.data, p.data_cap + 8);
+                        for (const hst::InPlan& P : inplans)
+                            if (p.data_cap < P.bufs[6].bytes) return 70;
+                    } else {
+                        out.add(p.values, p.values_cap + 8);
+                        out.add(p.validity, dfmi::bitmap_bytes(std::max<int64_t>(crows, 1)) + 8);
+                        if (p.values_cap < (size_t)crows * (size_t)dfmi::type_width(S.otype[o])) return 71;
+                    }
+                }
+                if (!out.ok(O.bytes) || O.bytes % 256 || O.n_bm != 4) return 72;  // Float64, Boolean x 2, Int8
+            }
+        }
+    // hb_layout over the three batches at once
+    PlanBatch b0(0, false), b1(1, true), b2(1025, false);
+    const dfmi_batch ins[3] = {b0.batch, b1.batch, b2.batch};
+    hst::HBLayout Lo;
+    hst::hb_layout(pred, projs, 4, ins, 3, Lo);
+    Regions in, out;
+    for (int b = 0; b < 3; ++b)
+        for (int c = 0; c < 4; ++c) {
+            const hst::HBLayout::In& L = Lo.lay[(size_t)b * 4 + c];
+            const dfmi::ColBytes cb = dfmi::col_bytes(ins[b].columns[c], ins[b].num_rows);
+            if (L.nval != cb.values || L.noff != cb.offsets) return 73;
+            if (L.nvld != (ins[b].columns[c].null_count > 0 ? cb.validity : 0)) return 74;  // no nulls: not staged
+            if (L.nval) in.add(L.val, L.nval);
+            if (L.noff) in.add(L.off, L.noff);
+            if (L.nvld) in.add(L.vld, L.nvld);
+            const hst::HBLayout::Out& O = Lo.olay[(size_t)b * 4 + c];
+            const int64_t n = ins[b].num_rows;
+            if (c == 2) {
+                out.add(O.off, (size_t)(n + 1) * 4);
+                out.add(O.dat, std::max<size_t>(O.ndat, 1));
+                if (O.ndat != cb.values) return 75;
+            } else if (n) {
+                out.add(O.val, c == 1 ? dfmi::bitmap_bytes(n) : (size_t)n * (size_t)dfmi::type_width(Lo.otype[c]));
+            }
+            if (n) out.add(O.vld, dfmi::bitmap_bytes(n));
+        }
+    if (!in.ok(Lo.in_bytes) || Lo.IB < Lo.in_bytes || Lo.IB % 256) return 76;
+    // the outputs' size, which dfmi_host_batches_output_bytes reports, holds every output region
+    if (!out.ok(Lo.out_bytes) || Lo.OB < Lo.out_bytes || Lo.OB % 256 || Lo.H < 3 * 256 || Lo.H % 256 || Lo.MB % 256) return 77;
+    // ragged / mixed batches are refused with the shared check's texts
+    PlanBatch bad(7, false);
+    bad.cols[3].length = 6;
+    const dfmi_batch two[2] = {b2.batch, bad.batch};
+    try {
+        hst::hb_layout(pred, projs, 4, two, 2, Lo);
+        return 78;
+    } catch (const dfmi::Fail& f) {
+        if (f.msg != "ragged batch") return 79;
+    }
+    dfmi_program_free(pred);
+    for (dfmi_program* p : projs) dfmi_program_free(p);
+    printf("plans: %d chunk plans and one host-batches layout checked\n", plans);
+    return 0;
+}
+
+// Pool::run with 0, 1 and 1000 tasks at 1 and 4 ways, twice in a row on one
+// pool: each task runs exactly once.
+int check_pool() {
+    for (int ways : {1, 4}) {
+        hst::Pool pool(ways - 1);
+        if (pool.ways() != ways) return 80;
+        for (int round = 0; round < 2; ++round)
+            for (int nt : {0, 1, 1000}) {
+                std::vector<int> ran((size_t)nt, 0);  // (task i alone writes ran[i])
+                hst::Tasks tasks;
+                for (int i = 0; i < nt; ++i) tasks.emplace_back([&ran, i] { ++ran[(size_t)i]; });
+                pool.run(tasks);
+                for (int r : ran)
+                    if (r != 1) return 81;
+            }
+    }
+    // the copy tasks: pieces that cover the bytes exactly once
+    std::vector<uint8_t> src((size_t)9 << 20), dst(src.size() + 1, 0);
+    for (size_t i = 0; i < src.size(); ++i) src[i] = (uint8_t)(i * 31 + (i >> 12));
+    std::vector<int32_t> off(3 << 18), reb(off.size() + 1, -1);
+    for (size_t i = 0; i < off.size(); ++i) off[i] = (int32_t)i;
+    hst::Pool pool(3);
+    hst::Tasks tasks;
+    hst::add_copy(tasks, dst.data(), src.data(), src.size(), pool.ways());
+    hst::add_copy_rebase(tasks, reb.data(), off.data(), off.size(), 1000, pool.ways());
+    if (tasks.size() < 2) return 82;
+    pool.run(tasks);
+    if (memcmp(dst.data(), src.data(), src.size()) || dst[src.size()] != 0) return 83;
+    for (size_t i = 0; i < off.size(); ++i)
+        if (reb[i] != (int32_t)i + 1000) return 84;
+    if (reb[off.size()] != -1) return 85;
+    printf("pool: every task ran once\n");
+    return 0;
+}
+
 }  // namespace
 
 int main() {
@@ -540,6 +825,10 @@ int main() {
     if (int rc = check_csv()) return rc;
     if (int rc = check_aggregates()) return rc;
     if (int rc = check_malformed_partials()) return rc;
+    if (int rc = check_bitmaps()) return rc;
+    if (int rc = check_chunk_rows()) return rc;
+    if (int rc = check_plans()) return rc;
+    if (int rc = check_pool()) return rc;
     printf("sanitize driver: clean\n");
     return 0;
 }

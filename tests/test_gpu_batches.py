@@ -336,3 +336,23 @@ def test_relation_results_are_block_arrays_and_keep_inputs_alive():
                                               Column(2))]
     for d, (_, r) in zip(first.columns, oracle_filter_project(s, bs[0], pred, projs)):
         assert_same(d, r)
+
+
+def test_host_results_outlive_their_context():
+    """A dfmi_host_result may outlive its context (the pinned pool is shared
+    by a context and the results it made): a context of its own, a 2,000-row
+    C2 call in four 512-row chunks (DFMI_HOST_CHUNK_ROWS=512) and a 1024-row
+    one, the context destroyed, then both results read, compared with numpy
+    and freed. In a child process (tests/host_result_lifetime.py says why,
+    and why the chunked call comes first)."""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, DFMI_HOST_PROFILE="1")
+    env.pop("DFMI_HOST_CHUNK_ROWS", None)
+    r = subprocess.run([sys.executable, os.path.join(here, "host_result_lifetime.py")], capture_output=True, text=True,
+                       timeout=120, env=env)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "results outlived their context" in r.stdout
+    assert "dfmi host: 4 chunks of 512 rows" in r.stderr and "dfmi host: 1 chunks of 1024 rows" in r.stderr, r.stderr

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of zero-copy inputs on the small host-batch calls (host_batch.cpp
+# A/B of zero-copy inputs on the small host-batch calls (host_batches.cpp
 # DFMI_HOST_ZC): the batches bench lines, alternating variants twice.
 set -o pipefail
 mkdir -p gpurun_out
