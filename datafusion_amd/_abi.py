@@ -33,6 +33,7 @@ DFMI_FLAG_EXT_CAST = 0x4
 DFMI_FLAG_EXT_IS_NULL = 0x8
 DFMI_FLAG_EXT_AGGREGATE = 0x10
 DFMI_FLAG_EXT_SORT = 0x20
+DFMI_FLAG_EXT_SCALAR_FUNCTIONS = 0x40
 
 # dfmi_agg_fn (AggregateType, expression.rs:33-40)
 DFMI_AGG_MIN = 0
@@ -139,6 +140,7 @@ EXPORTED = [
     "dfmi_host_batches_output_bytes",
     "dfmi_filter_project_host_batches_into",
     "dfmi_compile_scalar_expr",
+    "dfmi_scalar_function_meta",
     "dfmi_program_name",
     "dfmi_program_type",
     "dfmi_program_free",
@@ -272,6 +274,9 @@ def lib() -> C.CDLL:
     L.dfmi_compile_scalar_expr.argtypes = [C.POINTER(dfmi_expr_node), C.c_int32, C.POINTER(dfmi_schema),
                                            C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(dfmi_error)]
     L.dfmi_compile_scalar_expr.restype = C.c_int32
+    L.dfmi_scalar_function_meta.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.dfmi_scalar_function_meta.restype = C.c_int32
     L.dfmi_program_name.argtypes = [C.c_void_p]
     L.dfmi_program_name.restype = C.c_char_p
     L.dfmi_program_type.argtypes = [C.c_void_p]

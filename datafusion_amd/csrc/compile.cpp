@@ -34,6 +34,36 @@ static const char* op_debug(int op) {
 
 bool is_numeric_type(int t) { return t >= DFMI_TYPE_INT8 && t <= DFMI_TYPE_FLOAT64; }
 
+// Built-in scalar functions (DFMI_FLAG_EXT_SCALAR_FUNCTIONS). Names are
+// lower-case and matched exactly; the SQL signature is Float64 throughout
+// (the reference's one example, sqrt(Float64) -> Float64, sqlplanner.rs:761).
+// A new function is one row here plus one device helper dfmi::fn_<name> in
+// jit_skeleton.hip (at most two arguments: IrNode::l / r).
+namespace {
+struct ScalarFn {
+    const char* name;
+    int arity;
+    int arg_type;     // declared type of every parameter
+    int return_type;
+};
+const ScalarFn kScalarFns[] = {
+    {"sqrt", 1, DFMI_TYPE_FLOAT64, DFMI_TYPE_FLOAT64},  {"abs", 1, DFMI_TYPE_FLOAT64, DFMI_TYPE_FLOAT64},
+    {"floor", 1, DFMI_TYPE_FLOAT64, DFMI_TYPE_FLOAT64}, {"ceil", 1, DFMI_TYPE_FLOAT64, DFMI_TYPE_FLOAT64},
+    {"round", 1, DFMI_TYPE_FLOAT64, DFMI_TYPE_FLOAT64}, {"trunc", 1, DFMI_TYPE_FLOAT64, DFMI_TYPE_FLOAT64},
+    {"mod", 2, DFMI_TYPE_FLOAT64, DFMI_TYPE_FLOAT64},
+};
+constexpr int kNumScalarFns = (int)(sizeof kScalarFns / sizeof *kScalarFns);
+
+int find_scalar_fn(const char* name, int64_t len) {
+    if (!name || len < 0) return -1;
+    for (int i = 0; i < kNumScalarFns; ++i)
+        if ((int64_t)strlen(kScalarFns[i].name) == len && !memcmp(kScalarFns[i].name, name, (size_t)len)) return i;
+    return -1;
+}
+}  // namespace
+
+const char* scalar_fn_name(int id) { return (id >= 0 && id < kNumScalarFns) ? kScalarFns[id].name : ""; }
+
 // Rust (2018) float formatting: shortest round-trip digits, plain decimal;
 // Debug appends ".0" to integral values, Display drops the sign of -0.
 std::string rust_float(double v, bool f32, bool debug) {
@@ -311,6 +341,37 @@ int compile_node(const Builder& b, int t, const dfmi_schema& s, uint32_t flags, 
                 break;
             }
             throw CompileError{DFMI_ERR_EXECUTION, "expression " + expr_debug(b, t)};
+        case DFMI_EXPR_SCALAR_FUNCTION: {
+            if (!(flags & DFMI_FLAG_EXT_SCALAR_FUNCTIONS))
+                throw CompileError{DFMI_ERR_EXECUTION, "expression " + expr_debug(b, t)};
+            // extension: a built-in of the registry; arguments in order, their
+            // ordinals before the node's (as for a binary operator)
+            const std::string fname(n.str ? n.str : "", n.str && n.str_len > 0 ? (size_t)n.str_len : 0);
+            const int id = find_scalar_fn(n.str, n.str_len);
+            if (id < 0) throw CompileError{DFMI_ERR_EXECUTION, "Invalid function '" + fname + "'"};
+            const ScalarFn& f = kScalarFns[id];
+            if ((int)kids.size() != f.arity)
+                throw CompileError{DFMI_ERR_EXECUTION, "Function '" + fname + "' expects " + std::to_string(f.arity) +
+                                                           " arguments, got " + std::to_string(kids.size())};
+            int arg[2] = {-1, -1};
+            for (int i = 0; i < f.arity; ++i) arg[i] = compile_node(b, kids[i], s, flags, p);
+            // Float64 as declared, or the same function computed in Float32
+            bool ok = n.data_type == DFMI_TYPE_FLOAT64 || n.data_type == DFMI_TYPE_FLOAT32;
+            for (int i = 0; i < f.arity; ++i) ok = ok && p.ir[arg[i]].type == n.data_type;
+            if (!ok) {
+                std::string sig;
+                for (int i = 0; i < f.arity; ++i) sig += std::string(i ? ", " : "") + type_debug(p.ir[arg[i]].type);
+                throw CompileError{DFMI_ERR_EXECUTION, "Function '" + fname + "' is not supported for (" + sig +
+                                                           ") -> " + type_debug(n.data_type)};
+            }
+            ir.kind = IR_FN;
+            ir.fn = id;
+            ir.type = n.data_type;
+            ir.l = arg[0];
+            ir.r = arg[1];
+            ir.name = expr_debug(b, t);
+            break;
+        }
         default:
             throw CompileError{DFMI_ERR_EXECUTION, "expression " + expr_debug(b, t)};
     }
@@ -369,6 +430,17 @@ extern "C" int32_t dfmi_compile_scalar_expr(const dfmi_expr_node* nodes, int32_t
         return e.code;
     }
     *out = p;
+    return DFMI_OK;
+}
+
+extern "C" int32_t dfmi_scalar_function_meta(const char* name, int32_t name_len, int32_t* arg_types,
+                                             int32_t max_args, int32_t* num_args, int32_t* return_type) {
+    const int id = find_scalar_fn(name, name_len);
+    if (id < 0) return DFMI_ERR_EXECUTION;
+    const ScalarFn& f = kScalarFns[id];
+    for (int i = 0; arg_types && i < f.arity && i < max_args; ++i) arg_types[i] = f.arg_type;
+    if (num_args) *num_args = f.arity;
+    if (return_type) *return_type = f.return_type;
     return DFMI_OK;
 }
 

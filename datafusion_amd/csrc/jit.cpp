@@ -203,6 +203,19 @@ struct Gen {
             o << "    if (!" << v << "_n) " << v << " = (" << ctype(to) << ")0;\n";
             return Val{v, v + "_n"};
         }
+        if (n.kind == IR_FN) {  // extension: built-in function -- null if any argument is (zero slot), no errors
+            const Val a = emit(p, n.l, ord_base, act);
+            const Val b = n.r >= 0 ? emit(p, n.r, ord_base, act) : Val{"", "true"};
+            const std::string ct = ctype(n.type);
+            const std::string v = t();
+            o << "    " << ct << " " << v << " = dfmi::fn_" << scalar_fn_name(n.fn) << "<" << ct << ">(" << a.v
+              << (n.r >= 0 ? ", " + b.v : "") << ");\n";
+            if (a.n == "true" && b.n == "true") return Val{v, "true"};
+            const std::string nn = a.n == "true" ? b.n : (b.n == "true" ? a.n : "(" + a.n + " && " + b.n + ")");
+            o << "    const bool " << v << "_n = " << nn << ";\n";
+            o << "    if (!" << v << "_n) " << v << " = (" << ct << ")0;\n";
+            return Val{v, v + "_n"};
+        }
         const int ord = ord_base + n.ordinal;
         if (n.rt_code) {
             // the reference evaluates both children before failing here

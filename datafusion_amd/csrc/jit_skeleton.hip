@@ -236,6 +236,126 @@ __device__ __forceinline__ T sse_nan(T r, T a, T b) {
     }
 }
 
+// The one-argument form: a NaN argument comes back quieted (sign and payload
+// kept), an invalid operation on a non-NaN argument gives the default NaN.
+template <typename T>
+__device__ __forceinline__ T sse_nan1(T r, T a) {
+    return sse_nan<T>(r, a, a);
+}
+
+// Scalar function extension (DFMI_FLAG_EXT_SCALAR_FUNCTIONS): one helper
+// fn_<name><T> per row of compile.cpp's registry, T = float / double, with the
+// values of Rust's f32 / f64 methods on x86-64 bit for bit (include/dfmi.h).
+// Plain C++ and builtins only; nothing here depends on a math library.
+template <typename T>
+struct FBits;
+template <>
+struct FBits<double> {
+    typedef u64 U;
+    static constexpr int MB = 52, EMAX = 0x7ff;  // mantissa bits, all-ones exponent
+};
+template <>
+struct FBits<float> {
+    typedef u32 U;
+    static constexpr int MB = 23, EMAX = 0xff;
+};
+
+// sqrt: correctly rounded over the whole range. Float32 goes through the
+// Float64 square root: the 53-bit root of a 24-bit value rounds to the same
+// Float32 as the exact root (53 >= 2 * 24 + 2), subnormals included, whatever
+// the Float32 sqrt instruction's accuracy.
+template <typename T>
+__device__ __forceinline__ T fn_sqrt(T x) {
+    return sse_nan1<T>((T)__builtin_sqrt((double)x), x);
+}
+
+// abs: the sign bit cleared, nothing else (a NaN is not quieted).
+template <typename T>
+__device__ __forceinline__ T fn_abs(T x) {
+    typedef typename FBits<T>::U U;
+    return __builtin_bit_cast(T, (U)(__builtin_bit_cast(U, x) & (U)~((U)1 << (8 * sizeof(T) - 1))));
+}
+
+// floor / ceil / trunc: exact; a zero result keeps the argument's sign.
+template <typename T>
+__device__ __forceinline__ T fn_floor(T x) {
+    if constexpr (sizeof(T) == 8) return sse_nan1<T>(__builtin_floor(x), x);
+    else return sse_nan1<T>(__builtin_floorf(x), x);
+}
+template <typename T>
+__device__ __forceinline__ T fn_ceil(T x) {
+    if constexpr (sizeof(T) == 8) return sse_nan1<T>(__builtin_ceil(x), x);
+    else return sse_nan1<T>(__builtin_ceilf(x), x);
+}
+template <typename T>
+__device__ __forceinline__ T fn_trunc(T x) {
+    if constexpr (sizeof(T) == 8) return sse_nan1<T>(__builtin_trunc(x), x);
+    else return sse_nan1<T>(__builtin_truncf(x), x);
+}
+
+// round: half away from zero. x - trunc(x) is exact, and so is t +- 1 where
+// a fraction exists (|x| < 2^MB); floor(|x| + 0.5) would round
+// 0.49999999999999994 up.
+template <typename T>
+__device__ __forceinline__ T fn_round(T x) {
+    const T t = fn_trunc<T>(x);
+    const T d = x - t;  // NaN for an infinity: no step
+    const T step = fn_abs<T>(d) >= (T)0.5 ? (x < (T)0 ? (T)-1 : (T)1) : (T)0;
+    return sse_nan1<T>(step != (T)0 ? t + step : t, x);
+}
+
+// mod: C fmod by long division on the mantissas -- exact, the sign of x,
+// |result| < |y|. One quotient bit per step, so the step count is the
+// difference of the exponents (up to ~2100 for 1e308 mod 5e-324). y = +-0 or
+// x = +-inf is an invalid operation (default NaN), not an error.
+template <typename T>
+__device__ __forceinline__ T fn_mod(T x, T y) {
+    typedef typename FBits<T>::U U;
+    constexpr int MB = FBits<T>::MB, W = 8 * (int)sizeof(T);
+    constexpr U ONE = (U)1 << MB, SIGN = (U)1 << (W - 1), INF = (U)FBits<T>::EMAX << MB;
+    const U ux = __builtin_bit_cast(U, x), uy = __builtin_bit_cast(U, y);
+    const U ax = ux & (U)~SIGN, ay = uy & (U)~SIGN, sx = ux & SIGN;
+    if (ax >= INF || ay > INF || ay == 0)  // x infinite or NaN, y NaN, y zero
+        return sse_nan<T>(__builtin_bit_cast(T, (U)(INF | (ONE >> 1))), x, y);
+    if (ax < ay) return x;  // (an infinite y too)
+    if (ax == ay) return __builtin_bit_cast(T, sx);
+    // mantissas with the leading bit at MB (subnormals normalised), exponents
+    int ex = (int)(ax >> MB), ey = (int)(ay >> MB);
+    U mx = ax & (ONE - 1), my = ay & (ONE - 1);
+    auto lead = [](U m) {  // left shift that brings m's top set bit to MB (m != 0)
+        if constexpr (sizeof(U) == 8) return __builtin_clzll(m) - (W - 1 - MB);
+        else return __builtin_clz(m) - (W - 1 - MB);
+    };
+    if (ex == 0) {
+        const int s = lead(mx);
+        mx <<= s;
+        ex = 1 - s;
+    } else {
+        mx |= ONE;
+    }
+    if (ey == 0) {
+        const int s = lead(my);
+        my <<= s;
+        ey = 1 - s;
+    } else {
+        my |= ONE;
+    }
+    // mx < 2 * my before every step
+    for (int i = ex - ey; i > 0; --i) {
+        if (mx >= my) mx -= my;
+        mx <<= 1;
+    }
+    if (mx >= my) mx -= my;
+    if (mx == 0) return __builtin_bit_cast(T, sx);
+    const int s = lead(mx);
+    mx <<= s;
+    const int e = ey - s;
+    // e <= 0: a subnormal result; the bits shifted out are zero (the remainder
+    // is a multiple of y's last place, itself a multiple of the smallest subnormal)
+    const U r = e > 0 ? (U)(((U)e << MB) | (mx & (ONE - 1))) : (U)(mx >> (1 - e));
+    return __builtin_bit_cast(T, (U)(sx | r));
+}
+
 // iN::MIN as a value of T (signed T only).
 template <typename T>
 __device__ __forceinline__ constexpr T int_min() {

@@ -1,6 +1,7 @@
 // Build-time check of jit_skeleton.hip: instantiates every skeleton template
 // with a representative generated body (one Float64 predicate, a gathered
-// column, a Utf8 gather, integer division at several widths), so a broken skeleton fails `make` rather than the
+// column, a Utf8 gather, integer division at several widths, every scalar
+// function helper), so a broken skeleton fails `make` rather than the
 // first query compile on the GPU. Not linked into libdfmi.so.
 #include <hip/hip_runtime.h>
 
@@ -52,4 +53,19 @@ extern "C" __global__ __launch_bounds__(512) void dfmi_skeleton_check(const dfmi
     if (tid == 0 && dfmi::bitmap_word(A.valid[0], 0, A.n_rows) == 7)
         A.totals[0] = (u64)dfmi::idiv<i64>((i64)A.lits[1], (i64)A.lits[2]) +
                       (u64)dfmi::idiv<i8>((i8)A.lits[1], dfmi::int_min<i8>()) + dfmi::idiv<u16>((u16)A.lits[1], 3);
+    // scalar function extension: every helper, Float64 and Float32
+    {
+        const double x = dfmi::f64(c0[0]), y = dfmi::f64(A.lits[3]);
+        const float xf = __builtin_bit_cast(float, (u32)c0[1]), yf = __builtin_bit_cast(float, (u32)A.lits[3]);
+        const double d = dfmi::fn_mod<double>(
+            dfmi::fn_sqrt<double>(x) + dfmi::fn_abs<double>(x) + dfmi::fn_floor<double>(x) + dfmi::fn_ceil<double>(x) +
+                dfmi::fn_round<double>(x) + dfmi::fn_trunc<double>(x), y);
+        const float f = dfmi::fn_mod<float>(
+            dfmi::fn_sqrt<float>(xf) + dfmi::fn_abs<float>(xf) + dfmi::fn_floor<float>(xf) + dfmi::fn_ceil<float>(xf) +
+                dfmi::fn_round<float>(xf) + dfmi::fn_trunc<float>(xf), yf);
+        if (base + tid < A.n_rows) {
+            ((double*)A.out[1])[base + tid] = d;
+            ((float*)A.out[2])[base + tid] = f;
+        }
+    }
 }

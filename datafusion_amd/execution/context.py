@@ -158,8 +158,21 @@ class ExecutionContext:
         return ds.schema() if ds is not None else None
 
     def function_meta(self, name: str):
-        """ExecutionContextSchemaProvider::get_function_meta (context.rs:222-224): unimplemented!()."""
-        raise ExecutionError("panic", "not yet implemented")
+        """ExecutionContextSchemaProvider::get_function_meta (context.rs:222-224): unimplemented!().
+        Under DFMI_FLAG_EXT_SCALAR_FUNCTIONS: (argument types, return type) of a
+        built-in function from the library's registry, None for an unknown name
+        (the planner then raises its own "Invalid function")."""
+        import ctypes as C
+
+        from .. import _abi
+        if not (self.flags & _abi.DFMI_FLAG_EXT_SCALAR_FUNCTIONS):
+            raise ExecutionError("panic", "not yet implemented")
+        raw = name.encode("utf-8")
+        args = (C.c_int32 * 8)()
+        nargs, ret = C.c_int32(0), C.c_int32(0)
+        if _abi.lib().dfmi_scalar_function_meta(raw, len(raw), args, len(args), C.byref(nargs), C.byref(ret)) != 0:
+            return None
+        return [DataType(args[i]) for i in range(nargs.value)], DataType(ret.value)
 
     def execute(self, plan) -> Relation:
         """context.rs:103-163."""

@@ -30,7 +30,9 @@ extern "C" {
 /* Version of this header's structs and entry points. 2: dfmi_column.offset
  * (arrow ArrayData::offset), dfmi_abi_version(), the caller-owned output form
  * dfmi_filter_project_host_batches_into. 4: dfmi_sort_batches
- * (DFMI_FLAG_EXT_SORT). A binding compares the library's
+ * (DFMI_FLAG_EXT_SORT). Still 4 with DFMI_FLAG_EXT_SCALAR_FUNCTIONS: the
+ * change is additive (one flag bit, one new function, no struct change), so
+ * a version-4 binding keeps working. A binding compares the library's
  * dfmi_abi_version() with the constant it was built against. */
 #define DFMI_ABI_VERSION 4
 
@@ -195,6 +197,52 @@ typedef struct dfmi_expr_node {
                                            of every input row by the key list and / or the
                                            first n rows, dfmi_sort_batches below, semantics
                                            in DESIGN.md §2 */
+
+#define DFMI_FLAG_EXT_SCALAR_FUNCTIONS 0x40u
+/* Expr::ScalarFunction (DFMI_EXPR_SCALAR_FUNCTION; planned by sqlplanner.rs:330-350,
+ * executed nowhere in the reference) instead of the compile error
+ * "expression NAME(...)": the built-in functions
+ *     sqrt abs floor ceil round trunc   (one argument)      mod   (two arguments)
+ * with the SQL signature (Float64, ...) -> Float64 that dfmi_scalar_function_meta
+ * below reports to the planner. Names are lower-case and matched exactly.
+ * The node's `column` is the argument count, `str` the name and `data_type`
+ * the return type; the arguments precede it in postfix order. The compiler
+ * accepts Float64, or Float32 (every argument and data_type the same one of
+ * the two; the Float32 form is computed in Float32).
+ * Compile-time errors, all DFMI_ERR_EXECUTION:
+ *     Invalid function 'NAME'
+ *     Function 'NAME' expects N arguments, got M
+ *     Function 'NAME' is not supported for (T1, T2) -> R
+ * The program's name is the expression's Debug text, e.g.
+ * "sqrt(CAST(#3 AS Float64))". The result is null where any argument is null
+ * (value slot zero), and no function raises a run-time error. Values are
+ * those of Rust's f64 / f32 methods on x86-64, bit for bit:
+ *   sqrt   correctly rounded, subnormals included; sqrt(-0.0) = -0.0; a negative
+ *          argument (-inf too) gives the default NaN 0xFFF8000000000000 /
+ *          0xFFC00000;
+ *   abs    clears the sign bit and nothing else (a NaN keeps its payload and
+ *          is not quieted);
+ *   floor ceil trunc   exact, a zero result keeps the argument's sign
+ *          (ceil(-0.5) = -0.0);
+ *   round  half away from zero (round(-0.5) = -1.0, round(-0.4) = -0.0);
+ *   mod    C fmod: exact, the sign of x, |result| < |y|. y = +-0 or x = +-inf
+ *          is an invalid operation and gives the default NaN -- NOT
+ *          DFMI_ERR_DIVIDE_BY_ZERO, which only the Divide operator raises.
+ * Except for abs, a NaN argument comes back quieted with sign and payload
+ * kept, the left argument's first (the rule of the math operators).
+ * Transcendental functions are left out on purpose: their results differ
+ * between math libraries. The flag adds one bit and one entry point and
+ * changes no struct, so DFMI_ABI_VERSION stays 4. */
+
+/* Signature of a built-in scalar function, for a binding's
+ * SchemaProvider::get_function_meta (sqlplanner.rs:330-350 casts each
+ * argument to arg_types[i]). Returns 0 and fills *num_args, *return_type and
+ * the first min(*num_args, max_args) entries of arg_types (dfmi_type values)
+ * for a known name; nonzero, with nothing written, for an unknown one (the
+ * planner then raises its own "Invalid function 'NAME'"). NULL outputs are
+ * skipped. Needs no context and no flag: it only reads the table. */
+int32_t dfmi_scalar_function_meta(const char* name, int32_t name_len, int32_t* arg_types,
+                                  int32_t max_args, int32_t* num_args, int32_t* return_type);
 
 /* Opaque compiled expression: the RuntimeExpr::Compiled of expression.rs:43-50. */
 typedef struct dfmi_program dfmi_program;
