@@ -34,12 +34,14 @@ DFMI_FLAG_EXT_IS_NULL = 0x8
 DFMI_FLAG_EXT_AGGREGATE = 0x10
 DFMI_FLAG_EXT_SORT = 0x20
 DFMI_FLAG_EXT_SCALAR_FUNCTIONS = 0x40
+DFMI_FLAG_EXT_AGG_AVG = 0x80
 
 # dfmi_agg_fn (AggregateType, expression.rs:33-40)
 DFMI_AGG_MIN = 0
 DFMI_AGG_MAX = 1
 DFMI_AGG_SUM = 2
 DFMI_AGG_COUNT = 3
+DFMI_AGG_AVG = 4
 
 STATUS_NAMES = {
     DFMI_ERR_EXECUTION: "ExecutionError",

@@ -56,7 +56,7 @@ HashDev& hashdev(dfmi_context* ctx, dfmi_agg_state* st) {
     int w = 1;  // word 0: the group's rows
     for (size_t j = 0; j < n; ++j) {
         H->off.push_back(w);
-        const bool fs = st->aggs[j]->fn == DFMI_AGG_SUM && is_float_type(st->aggs[j]->arg.type);
+        const bool fs = acc_fn(st->aggs[j]->fn) == DFMI_AGG_SUM && is_float_type(st->aggs[j]->arg.type);
         if (fs) H->foff.push_back(w + 4);
         w += 4 + (fs ? kAggLimbs : 0);
     }
@@ -245,7 +245,7 @@ void host_merge_rows(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<df
         }
         ++g[n].count;  // the group's selected rows
         for (size_t j = 0; j < n; ++j)
-            if (valid(nk + j, i)) host_accumulate(g[j], st->aggs[j]->fn, cols[nk + j].type, hv[nk + j].data(), i);
+            if (valid(nk + j, i)) host_accumulate(g[j], acc_fn(st->aggs[j]->fn), cols[nk + j].type, hv[nk + j].data(), i);
     }
     for (std::vector<Partial>* e : touched) {  // only the entries this call touched
         for (Partial& q : *e) normalize(q);
@@ -338,7 +338,7 @@ void accumulate_bucketed(dfmi_context* ctx, dfmi_agg_state* st, HashDev& H, cons
         sa.arg[j] = c;
         nullable = nullable || c.validity;
         ba.a[j].c = c;
-        ba.a[j].fn = st->aggs[j]->fn;
+        ba.a[j].fn = acc_fn(st->aggs[j]->fn);
         ba.a[j].off = H.off[j];
         ba.pcol[j] = -1;
         const bool needs = st->aggs[j]->fn != DFMI_AGG_COUNT && c.type != DFMI_TYPE_UTF8 && c.type != DFMI_TYPE_BOOLEAN;
@@ -593,7 +593,7 @@ void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<
         aa.sidx = H.sidx.as<int32_t>();
         for (size_t j = 0; j < n; ++j) {
             aa.a[j].c = cols[nk + j];
-            aa.a[j].fn = st->aggs[j]->fn;
+            aa.a[j].fn = acc_fn(st->aggs[j]->fn);
             aa.a[j].off = H.off[j];
         }
         aa.naggs = (int)n;
@@ -651,7 +651,10 @@ const unsigned long long* round_records(dfmi_context* ctx, const dfmi_agg_state*
     for (size_t j = 0; j < n; ++j) {
         ra.off[j] = H.off[j];
         const int t = st->aggs[j]->arg.type;
-        ra.kind[j] = st->aggs[j]->fn == DFMI_AGG_SUM && is_float_type(t) ? (t == DFMI_TYPE_FLOAT32 ? 2 : 1) : 0;
+        const int fn = st->aggs[j]->fn;
+        ra.kind[j] = acc_fn(fn) == DFMI_AGG_SUM && is_float_type(t)
+                         ? (t == DFMI_TYPE_FLOAT32 ? 2 : 1) + (fn == DFMI_AGG_AVG ? 2 : 0)
+                         : 0;
     }
     ra.ngroups = H.ngroups;
     ra.out = (unsigned long long*)H.bufs[HashDev::DrainRounded].reserve(H.ngroups * (1 + 4 * n) * 8);
@@ -857,7 +860,7 @@ void sort_flat(const dfmi_agg_state* st, FlatGroups& f) {
 // groupby.h; word 0 the group's rows).
 void rec_partial(const dfmi_agg_state* st, const FlatGroups& f, const uint64_t* rec, size_t j, Partial& q) {
     const uint64_t* w = rec + f.off[j];
-    const int fn = st->aggs[j]->fn;
+    const int fn = acc_fn(st->aggs[j]->fn);
     q.count = rec[0] - w[0];  // the group's rows minus its NULL arguments
     if (fn == DFMI_AGG_SUM && is_float_type(st->aggs[j]->arg.type)) {
         q.flags = (w[1] & 0xffffffffull) | (q.count > w[3] ? AGGF_NONNEGZERO : 0);
@@ -1048,7 +1051,7 @@ void emit_flat(const dfmi_agg_state* st, const FlatGroups& f, int64_t cap, dfmi_
             for (size_t j = 0; j < n; ++j) {
                 q.flags = q.key = q.isum = 0;  // (rec_partial sets count and, for a float SUM, every digit)
                 rec_partial(st, f, rec, j, q);
-                if (f.rounded && st->aggs[j]->fn == DFMI_AGG_SUM && is_float_type(st->aggs[j]->arg.type)) {
+                if (f.rounded && acc_fn(st->aggs[j]->fn) == DFMI_AGG_SUM && is_float_type(st->aggs[j]->arg.type)) {
                     const uint64_t* w = rec + f.off[j];
                     Rounded r;
                     memcpy(&r.v, &w[2], 8);

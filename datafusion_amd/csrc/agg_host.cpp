@@ -6,6 +6,8 @@
 // sanitizers.
 #include "agg_host.h"
 
+#include "avg_round.h"
+
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -17,13 +19,14 @@ namespace aggh {
 
 using namespace layout;
 
-static int agg_fn_of(const std::string& name) {
+static int agg_fn_of(const std::string& name, uint32_t flags) {
     std::string l = name;
     for (auto& c : l) c = (char)tolower((unsigned char)c);
     if (l == "min") return DFMI_AGG_MIN;
     if (l == "max") return DFMI_AGG_MAX;
     if (l == "count") return DFMI_AGG_COUNT;
     if (l == "sum") return DFMI_AGG_SUM;
+    if (l == "avg" && (flags & DFMI_FLAG_EXT_AGG_AVG)) return DFMI_AGG_AVG;
     return -1;
 }
 
@@ -75,8 +78,9 @@ void normalize(Partial& p) {
 // The exact sum (normalised digits, units of 2^-1074) rounded half-to-even
 // to a format of `prec` significand bits whose quantum is at least
 // 2^(qmin-1074); `zero` when the exact sum is 0. Result as a double (exact
-// for Float32 results).
-static double round_exact(const Partial& p, int prec, int qmin, double overflow_limit, bool* zero) {
+// for Float32 results). With `div` != 0 (AVG): the exact sum divided by `div`
+// and rounded once the same way (avg_round.h).
+static double round_exact(const Partial& p, int prec, int qmin, double overflow_limit, bool* zero, uint64_t div = 0) {
     // magnitude digits (two's complement negation of the digit string)
     int64_t d[kAggLimbs];
     const bool neg = p.limbs[kAggLimbs - 1] < 0;
@@ -102,6 +106,11 @@ static double round_exact(const Partial& p, int prec, int qmin, double overflow_
         }
     *zero = top < 0;
     if (top < 0) return 0.0;
+    if (div) {
+        const double v = avg_round_magnitude([&](int i) -> uint32_t { return (uint32_t)d[i]; }, top, div, prec, qmin,
+                                             overflow_limit);
+        return neg ? -v : v;
+    }
     auto bit = [&](int i) -> uint64_t { return i < 0 ? 0 : ((uint64_t)d[i >> 5] >> (i & 31)) & 1; };
     int msb = 32 * top;  // highest set bit (digits < 2^32 after normalisation)
     for (int b = 31; b >= 0; --b)
@@ -182,7 +191,8 @@ dfmi_agg_value finish_normalized(const dfmi_aggregate& a, const Partial& p, cons
     }
     const bool f32 = t == DFMI_TYPE_FLOAT32;
     const uint64_t qnan = f32 ? 0x7FC00000ull : 0x7FF8000000000000ull;
-    if (a.fn == DFMI_AGG_SUM) {
+    if (a.fn == DFMI_AGG_SUM || a.fn == DFMI_AGG_AVG) {  // (an AVG's argument is a float: dfmi_compile_aggregate)
+        const uint64_t div = a.fn == DFMI_AGG_AVG ? p.count : 0;
         if (!is_float_type(t)) {
             r.bits = narrow_int(p.isum, t);
         } else if ((p.flags & AGGF_NAN) || ((p.flags & AGGF_PINF) && (p.flags & AGGF_NINF))) {
@@ -197,7 +207,7 @@ dfmi_agg_value finish_normalized(const dfmi_aggregate& a, const Partial& p, cons
                 v = pre->v;
                 zero = pre->zero;
             } else {
-                v = f32 ? round_exact(p, 24, 925, 0x1p128, &zero) : round_exact(p, 53, 0, HUGE_VAL, &zero);
+                v = f32 ? round_exact(p, 24, 925, 0x1p128, &zero, div) : round_exact(p, 53, 0, HUGE_VAL, &zero, div);
             }
             if (zero) v = (p.flags & AGGF_NONNEGZERO) ? 0.0 : -0.0;
             if (f32) {
@@ -323,6 +333,7 @@ void host_accumulate_t(Partial& p, int fn, T v) {
 }
 
 void host_accumulate(Partial& p, int fn, int t, const uint8_t* vals, int64_t i) {
+    fn = acc_fn(fn);
     switch (t) {
         case DFMI_TYPE_INT8: return host_accumulate_t(p, fn, ((const int8_t*)vals)[i]);
         case DFMI_TYPE_INT16: return host_accumulate_t(p, fn, ((const int16_t*)vals)[i]);
@@ -483,12 +494,15 @@ extern "C" int32_t dfmi_compile_aggregate(const char* name, const dfmi_program* 
         if (!name || !arg || !out) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         // ExecutionContext::execute has no Aggregate arm (context.rs:161)
         if (!(flags & DFMI_FLAG_EXT_AGGREGATE)) throw Fail{DFMI_ERR_PANIC, "not yet implemented"};
-        const int fn = agg_fn_of(name);  // compile_expr's match (expression.rs:100-106)
+        const int fn = agg_fn_of(name, flags);  // compile_expr's match (expression.rs:100-106)
         if (fn < 0) throw Fail{DFMI_ERR_PANIC, std::string("not yet implemented: Unsupported aggregate function '") + name + "'"};
         const int want = fn == DFMI_AGG_COUNT ? DFMI_TYPE_UINT64 : arg->type;  // sqlplanner.rs:296-330
         if (return_type != want) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "aggregate return type does not match the planner's"};
         if (fn != DFMI_AGG_COUNT && !is_numeric_type(arg->type))
             throw Fail{DFMI_ERR_NOT_IMPLEMENTED, std::string("aggregate over ") + type_debug(arg->type)};
+        // the state keeps only a wrapping 64-bit integer sum: no exact sum to divide
+        if (fn == DFMI_AGG_AVG && !is_float_type(arg->type))
+            throw Fail{DFMI_ERR_NOT_IMPLEMENTED, std::string("AVG over ") + type_debug(arg->type) + ": cast the argument to Float64"};
         dfmi_aggregate* a = new (std::nothrow) dfmi_aggregate();
         if (!a) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "out of memory"};
         a->name = name;

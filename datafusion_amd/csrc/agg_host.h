@@ -66,6 +66,12 @@ struct Rounded {
     bool zero;
 };
 
+// The function an aggregate ACCUMULATES as: an AVG's state is a float SUM's
+// (exact digits and the non-null count); only the finish divides. Kernels,
+// generated sources and their cache keys see SUM, so SUM(e) and AVG(e) share
+// one code object.
+inline int acc_fn(int fn) { return fn == DFMI_AGG_AVG ? DFMI_AGG_SUM : fn; }
+
 bool is_float_type(int t);
 bool is_signed_type(int t);
 bool host_keyed(int t);

@@ -84,11 +84,11 @@ void build_agg_plan(const dfmi_agg_state* st, const dfmi_program* pred, const df
         for (const IrNode& nd : a->arg.ir)
             if (nd.rt_code) se.offer((uint64_t)(base + nd.ordinal) << 44, nd.rt_code, nd.rt_msg);
         jit::AggSpec s;
-        s.fn = a->fn;
+        s.fn = acc_fn(a->fn);  // (an AVG accumulates as a SUM: the same kernel source and cache key)
         s.prog = &a->arg;
         s.ord_base = base;
         s.arg_type = a->arg.type;
-        if (a->fn == DFMI_AGG_SUM && is_float_type(a->arg.type)) s.fslot = nf++;
+        if (s.fn == DFMI_AGG_SUM && is_float_type(a->arg.type)) s.fslot = nf++;
         B.plan.aggs.push_back(s);
         base += a->arg.length;
     }

@@ -201,13 +201,16 @@ hipError_t launch_buckets(const RankArgs& r, ScatterArgs s, BucketArgs b, hipStr
 // record without its exact-sum digits; a floating-point SUM's key word holds
 // its digits rounded once, half to even (agg_host.cpp round_exact restated:
 // kind 1 to a Float64, kind 2 to a Float32's value as a double), and its
-// flags word kRoundZero when the exact sum is 0.
+// flags word kRoundZero when the exact sum is 0. An AVG (kinds 3 and 4) is a
+// float SUM's record whose digits are first divided by the record's non-null
+// count, rows - nulls (avg_round.h, the text the host finish runs): one
+// rounding of the exact mean; a count of 0 (a null result) divides nothing.
 struct RoundArgs {
     const unsigned long long* acc;  // [ngroups][words]
     int32_t words;
     int32_t naggs;
     int32_t off[kMaxAggs];          // word offset of aggregate j in a record
-    int32_t kind[kMaxAggs];         // 0: copied; 1: Float64 SUM; 2: Float32 SUM
+    int32_t kind[kMaxAggs];         // 0: copied; 1: Float64 SUM; 2: Float32 SUM; 3: Float64 AVG; 4: Float32 AVG
     unsigned long long ngroups;
     unsigned long long* out;        // [ngroups][1 + 4 * naggs]
 };

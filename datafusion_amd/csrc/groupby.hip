@@ -14,6 +14,7 @@
 #include "../../include/dfmi.h"
 #include "groupby.h"
 #include "sort_key.h"
+#include "avg_round.h"
 #include "jit_skeleton.hip"
 
 namespace dfmi {
@@ -975,10 +976,13 @@ __global__ __launch_bounds__(256) void k_group_normalize(const NormArgs A) {
 // quantum of at least 2^(qmin-1074): aggregate.cpp normalize + round_exact,
 // step for step. The thread's digits 0 .. kAggLimbs-2 live in LDS (`d`, with a
 // stride of kRoundBlock words: consecutive threads, consecutive banks), the top
-// (sign) digit in a register.
+// (sign) digit in a register. With `div` != 0 (AVG) the magnitude is divided
+// by `div` and rounded once by avg_round.h's routine, the text the host runs:
+// it only reads the digits (no quotient is stored, the LDS does not grow).
 constexpr int kRoundBlock = 128;
 
-__device__ double round_digits(const u64* L, unsigned* d, int prec, int qmin, double overflow_limit, bool& zero) {
+__device__ double round_digits(const u64* L, unsigned* d, int prec, int qmin, double overflow_limit, bool& zero,
+                               u64 div = 0) {
     constexpr int K = kAggLimbs;
     long long c = 0;
     for (int i = 0; i < K - 1; ++i) {  // carry-normalise: digits in [0, 2^32), floor carries upward
@@ -1012,6 +1016,10 @@ __device__ double round_digits(const u64* L, unsigned* d, int prec, int qmin, do
             }
     zero = top < 0;
     if (top < 0) return 0.0;
+    if (div) {
+        const double v = avg_round_magnitude(D, top, div, prec, qmin, overflow_limit);
+        return neg ? -v : v;
+    }
     const unsigned lo = (unsigned)D(top);
     const int msb = 32 * top + (lo ? 31 - __builtin_clz(lo) : 0);
     int q = msb - (prec - 1) > qmin ? msb - (prec - 1) : qmin;
@@ -1056,10 +1064,13 @@ __global__ __launch_bounds__(kRoundBlock) void k_group_round(const RoundArgs A) 
         const u64* w = rec + A.off[j];
         u64* ow = o + 1 + 4 * j;
         u64 flags = w[1], key = w[2];
-        if (A.kind[j]) {
+        const int kind = A.kind[j];
+        // an AVG divides by the non-null count; a count of 0 is a null result: no division
+        const u64 div = kind >= 3 ? rec[0] - w[0] : 0ull;
+        if (kind && (kind < 3 || div)) {
             bool zero = false;
-            const double v = A.kind[j] == 2 ? round_digits(w + 4, dg + threadIdx.x, 24, 925, 0x1p128, zero)
-                                            : round_digits(w + 4, dg + threadIdx.x, 53, 0, __builtin_inf(), zero);
+            const double v = (kind & 1) ? round_digits(w + 4, dg + threadIdx.x, 53, 0, __builtin_inf(), zero, div)
+                                        : round_digits(w + 4, dg + threadIdx.x, 24, 925, 0x1p128, zero, div);
             key = __builtin_bit_cast(u64, v);
             if (zero) flags |= kRoundZero;
         }
@@ -1139,7 +1150,7 @@ __device__ __forceinline__ AggValue finish_value(const u64* rec, int off, int fn
     }
     const bool f32 = t == 10, flt = t == 10 || t == 11;
     const u64 qnan = f32 ? 0x7FC00000ull : 0x7FF8000000000000ull;
-    if (fn == DFMI_AGG_SUM) {
+    if (fn == DFMI_AGG_SUM || fn == DFMI_AGG_AVG) {  // (an AVG's key word: the mean, k_group_round)
         if (!flt) {
             r.bits = narrow_bits(w[3], t);
             return r;

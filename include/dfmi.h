@@ -234,6 +234,16 @@ typedef struct dfmi_expr_node {
  * between math libraries. The flag adds one bit and one entry point and
  * changes no struct, so DFMI_ABI_VERSION stays 4. */
 
+#define DFMI_FLAG_EXT_AGG_AVG      0x80u /* with DFMI_FLAG_EXT_AGGREGATE: the aggregate
+                                           function `avg` (planned by sqlplanner.rs:296 in
+                                           one arm with min / max / sum, executed nowhere
+                                           in the reference) instead of the panic
+                                           "Unsupported aggregate function 'avg'": the
+                                           exact mean rounded once, semantics in the
+                                           aggregate section below. One bit and one enum
+                                           value, no struct change: DFMI_ABI_VERSION
+                                           stays 4 */
+
 /* Signature of a built-in scalar function, for a binding's
  * SchemaProvider::get_function_meta (sqlplanner.rs:330-350 casts each
  * argument to arg_types[i]). Returns 0 and fills *num_args, *return_type and
@@ -473,6 +483,30 @@ int32_t dfmi_last_error_order(const dfmi_context* ctx, uint64_t* key);
  *   MIN/MAX(e): NaN values are skipped (a set of only NaNs gives the
  *             canonical NaN), -0.0 orders below +0.0;
  *   SUM/MIN/MAX over no non-null value is null.
+ *   AVG(e) (DFMI_FLAG_EXT_AGG_AVG together with DFMI_FLAG_EXT_AGGREGATE;
+ *             without the flag `avg` panics as in the reference; build-defined,
+ *             parity unpinned): e is Float64 or Float32 and the result has e's
+ *             type (sqlplanner.rs:301-303). With n the non-null values of e over
+ *             the selected rows: count = n; n = 0 gives null; a NaN input or
+ *             +inf with -inf gives SUM's canonical quiet NaN, otherwise an
+ *             infinite input gives that infinity; otherwise the exact rational
+ *             (exact sum) / n rounded half to even ONCE -- Float64: 53 bits,
+ *             quantum at least 2^-1074; Float32: 24 bits, quantum at least
+ *             2^-149; results in the subnormal range are rounded at the
+ *             subnormal quantum (AVG(5e-324, 0.0) = +0.0, a tie to even). It is
+ *             not fl(fl(SUM)/n), which rounds twice and overflows:
+ *             AVG(1.797e308, 1.797e308) is 1.797e308, and finite inputs never
+ *             give an infinity. A nonzero exact sum whose mean rounds to zero
+ *             keeps the sum's sign; an exact-zero sum follows SUM's rule (-0.0
+ *             only if every value is -0.0). n may be anything in [1, 2^63). Like
+ *             SUM it does not depend on row order, batch size or GPU count, and
+ *             it runs everywhere SUM does with the same bits; an AVG's partial
+ *             is a SUM's partial (no wire format changes) and an AVG takes one
+ *             of the four float-SUM slots of a state. An integer argument is
+ *             DFMI_ERR_NOT_IMPLEMENTED "AVG over <Type>: cast the argument to
+ *             Float64" (the state keeps only a wrapping 64-bit integer sum, so
+ *             there is no exact sum to divide): write AVG(CAST(c AS DOUBLE)).
+ *             Boolean and Utf8 arguments fail as they do for SUM.
  * GROUP BY (dfmi_agg_state_create_grouped / _multi): one to four key
  * expressions of any type the reference's values take -- Boolean, integer,
  * Float32 / Float64 or Utf8; per group the aggregates above. Groups come out
@@ -494,7 +528,8 @@ typedef enum dfmi_agg_fn {       /* AggregateType (expression.rs:33-40) */
     DFMI_AGG_MIN = 0,
     DFMI_AGG_MAX = 1,
     DFMI_AGG_SUM = 2,
-    DFMI_AGG_COUNT = 3
+    DFMI_AGG_COUNT = 3,
+    DFMI_AGG_AVG = 4             /* DFMI_FLAG_EXT_AGG_AVG; not an AggregateType of the reference */
 } dfmi_agg_fn;
 
 typedef struct dfmi_agg_value {
@@ -508,8 +543,8 @@ typedef struct dfmi_agg_value {
 typedef struct dfmi_aggregate dfmi_aggregate;
 
 /* compile_expr's AggregateFunction arm (expression.rs:81-116): `name` as the
- * SQL text spells it (min / max / sum / count, any case; anything else panics
- * in the reference: DFMI_ERR_PANIC), `argument` compiled by
+ * SQL text spells it (min / max / sum / count, any case, and avg with
+ * DFMI_FLAG_EXT_AGG_AVG; anything else panics in the reference: DFMI_ERR_PANIC), `argument` compiled by
  * dfmi_compile_scalar_expr, `return_type` the planner's (sqlplanner.rs:296-330:
  * the argument's type, UInt64 for count). */
 int32_t dfmi_compile_aggregate(const char* name, const dfmi_program* argument, int32_t return_type,
