@@ -35,6 +35,7 @@ DFMI_FLAG_EXT_AGGREGATE = 0x10
 DFMI_FLAG_EXT_SORT = 0x20
 DFMI_FLAG_EXT_SCALAR_FUNCTIONS = 0x40
 DFMI_FLAG_EXT_AGG_AVG = 0x80
+DFMI_FLAG_EXT_UTF8_ORDER = 0x100  # with DFMI_FLAG_EXT_UTF8_COMPARE: Utf8 <, <=, >, >=
 
 # dfmi_agg_fn (AggregateType, expression.rs:33-40)
 DFMI_AGG_MIN = 0

@@ -308,8 +308,11 @@ int compile_node(const Builder& b, int t, const dfmi_schema& s, uint32_t flags, 
             const int lt = p.ir[l].type, rt = p.ir[r].type;
             if (n.op >= DFMI_OP_EQ && n.op <= DFMI_OP_GT_EQ) {
                 ir.type = DFMI_TYPE_BOOLEAN;
+                // =, != with DFMI_FLAG_EXT_UTF8_COMPARE; <, <=, >, >= with
+                // DFMI_FLAG_EXT_UTF8_ORDER on top of it
                 const bool utf8_ok = (flags & DFMI_FLAG_EXT_UTF8_COMPARE) && lt == DFMI_TYPE_UTF8 &&
-                                     rt == DFMI_TYPE_UTF8 && (n.op == DFMI_OP_EQ || n.op == DFMI_OP_NOT_EQ);
+                                     rt == DFMI_TYPE_UTF8 &&
+                                     (n.op == DFMI_OP_EQ || n.op == DFMI_OP_NOT_EQ || (flags & DFMI_FLAG_EXT_UTF8_ORDER));
                 if (!((lt == rt && is_numeric_type(lt)) || utf8_ok)) {
                     ir.rt_code = DFMI_ERR_EXECUTION;
                     ir.rt_msg = "comparison_ops";

@@ -330,6 +330,9 @@ void build_plan_impl(const dfmi_program* pred, const dfmi_program* const* projs,
             const int g = atoi(e);
             if (g == 1 || g == 2 || g == 4 || g == 8) X.eq_dense = X.K % g == 0 ? -g : 0;
         }
+        // Utf8 ordering compares: head width, and the tile pre-pass off (per-row helper in the loop)
+        if (const char* e = getenv("DFMI_UTF8_ORD_H")) X.ord_h = atoi(e) == 8 ? 8 : 4;
+        if (const char* e = getenv("DFMI_UTF8_ORD_PRE")) X.ord_pre = atoi(e) & 1;
         if (const char* e = getenv("DFMI_UTF8_RING"))  // 0: off; > 0: on (slot chunks) where it applies
             if (pred && X.utf8_outs.size() == 1 && !X.pred_slots.empty() && X.M == 1) {
                 X.ring = atoi(e) > 1 ? atoi(e) : (atoi(e) == 1 ? kRingSlot : 0);
@@ -1051,13 +1054,16 @@ int32_t dfmi::filter_project_batches_staged(dfmi_context* ctx, const dfmi_progra
 // compile != 0, compiles it with hipRTC -- no device needed, so the CPU test
 // suite checks code generation for every expression shape it covers.
 // Returns the source length (the text is truncated to cap), or -status.
+// Flag bit 0x40000000: the coalesced-batches form; 0x20000000: the shape
+// chosen after the query's last large batch selected most rows (high_sel).
 extern "C" int64_t dfmi_internal_jit_check(const dfmi_program* pred, const dfmi_program* const* projs, int32_t np,
                                            const dfmi_batch* in, dfmi_out_column* outs, uint32_t flags,
                                            int32_t compile, char* buf, int64_t cap, dfmi_error* err) {
     return guarded_size(err, [&]() -> int64_t {
         if (!in || (np > 0 && !projs) || !outs) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         Built B;
-        build_plan(pred, projs, np, in, outs, flags & ~0x40000000u, B);
+        B.high_sel = (flags & 0x20000000u) != 0;  // as if the query's last large batch selected most rows
+        build_plan(pred, projs, np, in, outs, flags & ~0x60000000u, B);
         B.X.batched = (flags & 0x40000000u) != 0;  // the coalesced-batches form of the kernel
         const std::string src = jit::generate(B.plan, B.X);
         if (compile) (void)jit::compile_code(src, nullptr);

@@ -116,6 +116,9 @@ struct Gen {
     // (array name, utf8 slot, string literal index)
     bool tile_pre = false;
     std::vector<std::tuple<std::string, int, int>> pre_eq;
+    // ... and `col <ordering operator> literal` as three-way results
+    // (utf8_cmp_lit_tile); the operator is applied in the loop
+    std::vector<std::tuple<std::string, int, int>> pre_ord;
 
     Gen(const Plan& p, Launch& x) : P(p), X(x) {}
 
@@ -159,6 +162,53 @@ struct Gen {
         if (t == DFMI_TYPE_FLOAT64) return "__builtin_bit_cast(double, " + a + ")";
         if (t == DFMI_TYPE_FLOAT32) return "__builtin_bit_cast(float, (u32)" + a + ")";
         return "((" + std::string(ctype(t)) + ")" + a + ")";
+    }
+
+    // Utf8 ordering compare (DFMI_FLAG_EXT_UTF8_ORDER): bytewise, unsigned, a
+    // proper prefix first; nulls by cmp_opt as the numeric compares. A literal
+    // on the left is compared from the column's side with the mirrored
+    // operator (cmp_opt still sees the operands in their own order).
+    Val emit_utf8_order(const dfmi_program* p, const IrNode& n, const IrNode& L, const IrNode& R, int ord_base,
+                        const char* act) {
+        const int op = n.op;
+        const std::string v = t();
+        if (L.kind == IR_LIT && R.kind == IR_LIT) {  // folded: unsigned bytes, then the lengths
+            const size_t m = std::min(L.str.size(), R.str.size());
+            int c = m ? memcmp(L.str.data(), R.str.data(), m) : 0;
+            if (c == 0) c = L.str.size() < R.str.size() ? -1 : (L.str.size() > R.str.size() ? 1 : 0);
+            const bool r = op == DFMI_OP_LT ? c < 0 : op == DFMI_OP_LT_EQ ? c <= 0 : op == DFMI_OP_GT ? c > 0 : c >= 0;
+            o << "    const bool " << v << " = " << (r ? "true" : "false") << ";\n";
+            return Val{v, "true"};
+        }
+        const Val a = emit(p, n.l, ord_base, act);  // validity only
+        const Val b = emit(p, n.r, ord_base, act);
+        const std::string H = std::to_string(X.ord_h);
+        std::string res;
+        if (L.kind == IR_COL && R.kind == IR_COL) {
+            res = "dfmi::utf8_cmp_col<" + std::to_string(op) + ", " + H + ">(A, " + std::to_string(X.slot_of_utf8(L.col)) +
+                  ", " + std::to_string(X.slot_of_utf8(R.col)) + ", row)";
+        } else {
+            const bool lit_left = L.kind == IR_LIT;
+            const IrNode& C = lit_left ? R : L;
+            const IrNode& S = lit_left ? L : R;
+            static const int mirror[] = {DFMI_OP_GT, DFMI_OP_GT_EQ, DFMI_OP_LT, DFMI_OP_LT_EQ};
+            const std::string mop = std::to_string(lit_left ? mirror[op - DFMI_OP_LT] : op);
+            const int u = X.slot_of_utf8(C.col);
+            const int sl = strlit(S.str);
+            if (tile_pre && X.ord_pre) {
+                const std::string arr = "uo" + std::to_string(pre_ord.size()) + sfx;
+                pre_ord.emplace_back(arr, u, sl);
+                res = "dfmi::utf8_ord_tile<" + mop + ">(" + arr + ", k)";
+            } else {
+                res = "dfmi::utf8_cmp_lit<" + mop + ", " + H + ">(A, " + std::to_string(u) + ", row, " +
+                      std::to_string(sl) + ", A0.str + A0.str_off[" + std::to_string(sl) + "])";
+            }
+        }
+        if (a.n == "true" && b.n == "true")
+            o << "    const bool " << v << " = " << res << ";\n";
+        else
+            o << "    const bool " << v << " = dfmi::cmp_opt<" << op << ">(" << a.n << ", " << b.n << ", " << res << ");\n";
+        return Val{v, "true"};
     }
 
     // Emit node i of program p; act = C++ bool expression "row is evaluated".
@@ -229,8 +279,9 @@ struct Gen {
         }
         const int op = n.op;
         const IrNode& L = p->ir[n.l];
-        if (L.type == DFMI_TYPE_UTF8 && op <= DFMI_OP_GT_EQ) {  // extension: Utf8 =, !=
+        if (L.type == DFMI_TYPE_UTF8 && op <= DFMI_OP_GT_EQ) {  // extension: Utf8 =, !=, <, <=, >, >=
             const IrNode& R = p->ir[n.r];
+            if (op >= DFMI_OP_LT) return emit_utf8_order(p, n, L, R, ord_base, act);
             const bool eq = op == DFMI_OP_EQ;
             const std::string v = t();
             if (L.kind == IR_LIT && R.kind == IR_LIT) {
@@ -598,6 +649,7 @@ static std::vector<int> emit_predicate(Gen& g, std::ostringstream& o, const Plan
     const std::string head = o.str();
     g.tile_pre = true;
     g.pre_eq.clear();
+    g.pre_ord.clear();
     o << "  unsigned selm = 0;\n#pragma unroll\n  for (int k = 0; k < K; ++k) {\n";
     o << "    const i64 row = base + k * BLOCK + tid;\n    const bool in = row < A.n_rows;\n";
     const Val r = g.emit(P.pred, P.pred->root, 0, "in");
@@ -617,6 +669,7 @@ static std::vector<int> emit_predicate(Gen& g, std::ostringstream& o, const Plan
             << ", ux" << offs_name(u) << ");\n";
     };
     for (const auto& pe : g.pre_eq) load_offs(std::get<1>(pe));
+    for (const auto& pe : g.pre_ord) load_offs(std::get<1>(pe));
     for (int u : extra_offs) load_offs(u);
     for (const auto& [arr, u, sl] : g.pre_eq)
         if (X.eq_dense < 0)
@@ -630,6 +683,23 @@ static std::vector<int> emit_predicate(Gen& g, std::ostringstream& o, const Plan
         else
         pre << "  bool " << arr << "[K];\n  dfmi::utf8_eq_lit_tile<BLOCK, K>(A, " << u << ", " << sl << ", A0.str + A0.str_off["
             << sl << "], us" << offs_name(u) << ", ux" << offs_name(u) << ", lane, " << arr << ");\n";
+    // two ordering compares of one column (the bounds of a prefix range) share one fetch of the heads
+    for (size_t i = 0; i < g.pre_ord.size(); ++i) {
+        const auto& [arr, u, sl] = g.pre_ord[i];
+        const std::string tail = ", us" + offs_name(u) + ", ux" + offs_name(u) + ", lane, ";
+        if (i + 1 < g.pre_ord.size() && std::get<1>(g.pre_ord[i + 1]) == u) {
+            ++i;
+            const std::string& arr2 = std::get<0>(g.pre_ord[i]);
+            const int sl2 = std::get<2>(g.pre_ord[i]);
+            pre << "  unsigned " << arr << ", " << arr2 << ";\n  { const int l_[2] = {" << sl << ", " << sl2
+                << "}; const char* const q_[2] = {A0.str + A0.str_off[" << sl << "], A0.str + A0.str_off[" << sl2
+                << "]}; unsigned r_[2];\n    dfmi::utf8_cmp_lits_tile<BLOCK, K, " << X.ord_h << ", 2>(A, " << u
+                << ", l_, q_" << tail << "r_);\n    " << arr << " = r_[0]; " << arr2 << " = r_[1]; }\n";
+        } else {
+            pre << "  unsigned " << arr << ";\n  dfmi::utf8_cmp_lit_tile<BLOCK, K, " << X.ord_h << ">(A, " << u << ", "
+                << sl << ", A0.str + A0.str_off[" << sl << "]" << tail << arr << ");\n";
+        }
+    }
     if (!pre.str().empty()) {  // splice in front of the predicate loop
         const std::string loop = o.str().substr(head.size());
         o.str(head + pre.str() + loop);
@@ -1378,7 +1448,7 @@ std::string shape_key(int device, const Plan& P, const Launch& X) {
         put(k, (char)os.nullable);
     }
     const int tile[] = {X.K,  X.BLOCK,  X.waves_per_eu, X.R,     X.sleep,          X.spread,
-                        X.window, X.nt, X.gather,       X.late_proj, X.arena, (int)X.batched, X.M, X.KO, X.prestage, X.prefetch, X.gather_phases, X.image, X.dbuf, X.sparse, X.pairs, X.st16, X.proj_dense, X.hdr_out, X.ticket, X.early, X.ring, X.eq_dense, X.light_copy, X.direct_grp, X.long_copy};
+                        X.window, X.nt, X.gather,       X.late_proj, X.arena, (int)X.batched, X.M, X.KO, X.prestage, X.prefetch, X.gather_phases, X.image, X.dbuf, X.sparse, X.pairs, X.st16, X.proj_dense, X.hdr_out, X.ticket, X.early, X.ring, X.eq_dense, X.light_copy, X.direct_grp, X.long_copy, X.ord_h, X.ord_pre};
     k.append((const char*)tile, sizeof tile);
     for (int c : X.num_cols) {
         put(k, c);

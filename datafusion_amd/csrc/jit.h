@@ -78,6 +78,13 @@ struct Launch {
     // an LDS arena of eq_dense 16-byte chunks and compare from there (diagnostic A/B);
     // < 0: the register-resident dense form, -eq_dense slices' spans per load round
     int eq_dense = 0;
+    // Utf8 ordering compares (DFMI_FLAG_EXT_UTF8_ORDER): head bytes compared
+    // as one integer (4 or 8), and whether a filtered tile's `col OP literal`
+    // is evaluated tile-wide before the predicate loop (utf8_cmp_lit_tile) or
+    // per row inside it (diagnostic A/B: DFMI_UTF8_ORD_H, DFMI_UTF8_ORD_PRE;
+    // measured, DESIGN.md §6 "Utf8 ordering")
+    int ord_h = 4;
+    int ord_pre = 1;
     // Utf8 gather: the per-lane fallback copy (a slice whose span is over the
     // stage) as register-light unaligned 16-/4-byte moves instead of
     // utf8_copy's aligned 8-word chunks: C3 -1%, 40-200-byte strings -25%

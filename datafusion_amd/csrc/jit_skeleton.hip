@@ -527,6 +527,272 @@ __device__ __forceinline__ bool utf8_eq_col(const Args& A, int u, int v, i64 row
     return true;
 }
 
+// ---- utf8 order core: begin ------------------------------------------------
+// Utf8 ordering (DFMI_FLAG_EXT_UTF8_ORDER): byte strings compared as
+// sequences of unsigned bytes, a proper prefix first -- the GROUP BY / ORDER
+// BY key order (sort_key.h). Plain C++ between the two markers, no Args and
+// no wave intrinsics: tests/native/utf8_order_driver.cpp compiles this very
+// text for the host (it defines DFMI_ORD_FN, DFMI_ORD_TAIL, DFMI_ALIGNBYTE and the integer
+// typedefs) and runs it under the address sanitizer against a bytewise
+// reference.
+//
+// A string's head is its first m = min(own length, other length, H) bytes
+// read as one big-endian integer (H = 4 or 8, the bytes at and past m zero),
+// so one unsigned compare orders those m bytes. Equal heads that cover the
+// shorter string leave the lengths to decide; otherwise (rare: both strings
+// longer than H and equal in their first H bytes) the walk goes on from byte
+// H in big-endian steps of 8, 4 and 1 bytes, never reading at or past either
+// string's end.
+#ifndef DFMI_ORD_FN
+#define DFMI_ORD_FN __device__ __forceinline__
+#define DFMI_ORD_TAIL __device__ __forceinline__
+#define DFMI_ALIGNBYTE(hi, lo, sh) __builtin_amdgcn_alignbyte(hi, lo, sh)
+#endif
+
+template <int H>
+struct Utf8Head;
+template <>
+struct Utf8Head<4> {
+    typedef u32 W;
+};
+template <>
+struct Utf8Head<8> {
+    typedef u64 W;
+};
+
+DFMI_ORD_FN u32 utf8_bswap(u32 x) { return __builtin_bswap32(x); }
+DFMI_ORD_FN u64 utf8_bswap(u64 x) { return __builtin_bswap64(x); }
+
+// Mask of the m (0 .. sizeof(W)) leading bytes of a big-endian head.
+template <typename W>
+DFMI_ORD_FN W utf8_head_mask(int m) {
+    return m <= 0 ? (W)0 : (W)(~(W)0 << (8 * ((int)sizeof(W) - m)));
+}
+
+// Head of the m bytes held, in memory order, in the low bytes of `le`.
+template <typename W>
+DFMI_ORD_FN W utf8_head(W le, int m) {
+    return (W)(utf8_bswap(le) & utf8_head_mask<W>(m));
+}
+
+// The m (<= sizeof(W)) bytes at p as a head: reads exactly [p, p + m).
+template <typename W>
+DFMI_ORD_FN W utf8_head_at(const u8* p, int m) {
+    W le = 0;
+    if (m >= (int)sizeof(W)) {
+        __builtin_memcpy(&le, p, sizeof(W));  // any byte address
+    } else {
+        for (int i = 0; i < m; ++i) le |= (W)p[i] << (8 * i);
+    }
+    return utf8_head<W>(le, m);
+}
+
+// The m (1 .. sizeof(W)) bytes at byte `pos` of the 4-aligned buffer `ab`, as
+// the aligned 32-bit words holding them shifted into place (a column's bytes
+// `by` with by & 3 = bmis: ab = by - bmis, pos = row start + bmis -- a
+// uniform base plus a non-negative 32-bit offset per load). Reads only words
+// that hold one of those bytes; the bytes past m of the result are
+// unspecified (utf8_head masks them). m <= 0 reads nothing.
+template <typename W>
+DFMI_ORD_FN W utf8_head_window(const u8* ab, unsigned pos, int m) {
+    if (m <= 0) return (W)0;
+    const unsigned mis = pos & 3u, o0 = pos & ~3u;          // the word of byte 0
+    const unsigned last = (mis + (unsigned)m - 1u) >> 2;    // index of the word of byte m - 1
+    const u32 w0 = *(const u32*)(ab + o0);
+    const u32 w1 = *(const u32*)(ab + (o0 + 4u * (last < 1u ? last : 1u)));
+    const u32 lo = DFMI_ALIGNBYTE(w1, w0, mis);
+    if constexpr (sizeof(W) == 4) {
+        return lo;
+    } else {
+        const u32 w2 = *(const u32*)(ab + (o0 + 4u * last));
+        const u32 hi = DFMI_ALIGNBYTE(w2, w1, mis);
+        return (W)lo | ((W)hi << 32);
+    }
+}
+
+DFMI_ORD_FN u64 utf8_be64(const u8* p) {
+    u64 x;
+    __builtin_memcpy(&x, p, 8);
+    return __builtin_bswap64(x);
+}
+DFMI_ORD_FN u32 utf8_be32(const u8* p) {
+    u32 x;
+    __builtin_memcpy(&x, p, 4);
+    return __builtin_bswap32(x);
+}
+
+// The rare path: a and b agree in their first `from` bytes.
+DFMI_ORD_TAIL int utf8_cmp_tail(const u8* a, int la, const u8* b, int lb, int from) {
+    const int n = la < lb ? la : lb;
+    int i = from;
+    for (; i + 8 <= n; i += 8) {
+        const u64 x = utf8_be64(a + i), y = utf8_be64(b + i);
+        if (x != y) return x < y ? -1 : 1;
+    }
+    if (i + 4 <= n) {
+        const u32 x = utf8_be32(a + i), y = utf8_be32(b + i);
+        if (x != y) return x < y ? -1 : 1;
+        i += 4;
+    }
+    for (; i < n; ++i)
+        if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
+    return la < lb ? -1 : (la > lb ? 1 : 0);
+}
+
+// -1 / 0 / 1 for a < b / a == b / a > b, given the heads ha / hb of the
+// first min(la, lb, sizeof(W)) bytes of both.
+template <typename W>
+DFMI_ORD_FN int utf8_cmp3(W ha, W hb, const u8* a, int la, const u8* b, int lb) {
+    if (ha != hb) return ha < hb ? -1 : 1;
+    if (la <= (int)sizeof(W) || lb <= (int)sizeof(W))  // the heads cover the shorter string
+        return la < lb ? -1 : (la > lb ? 1 : 0);
+    return utf8_cmp_tail(a, la, b, lb, (int)sizeof(W));
+}
+
+template <int H>
+DFMI_ORD_FN int utf8_cmp_bytes(const u8* a, int la, const u8* b, int lb) {
+    typedef typename Utf8Head<H>::W W;
+    const int n = la < lb ? la : lb;
+    const int m = n < H ? n : H;
+    return utf8_cmp3<W>(utf8_head_at<W>(a, m), utf8_head_at<W>(b, m), a, la, b, lb);
+}
+
+// One row of the tile pre-pass against a literal of `len` bytes: `le` is the
+// utf8_head_window of the row's leading min(L, hq) bytes, `qh` the literal's
+// head of its hq = min(len, sizeof(W)) bytes (utf8_head_at). -1 / 0 / 1, or 2:
+// undecided -- both longer than the head and equal in it; the caller walks on
+// (utf8_cmp_tail from byte sizeof(W)) once the tile's head words are consumed.
+template <typename W>
+DFMI_ORD_FN int utf8_cmp_windowed(W le, W qh, int hq, int L, int len) {
+    const int m = L < hq ? L : hq;
+    const W hr = utf8_head<W>(le, m), hl = (W)(qh & utf8_head_mask<W>(m));
+    if (hr != hl) return hr < hl ? -1 : 1;
+    if (L <= (int)sizeof(W) || len <= (int)sizeof(W))  // the heads cover the shorter string
+        return L < len ? -1 : (L > len ? 1 : 0);
+    return 2;
+}
+
+// The ordering operator OP (DFMI_OP_LT = 2 .. DFMI_OP_GT_EQ = 5) of a
+// three-way result.
+template <int OP>
+DFMI_ORD_FN bool utf8_ord(int c) {
+    static_assert(OP >= 2 && OP <= 5, "an ordering operator");
+    if constexpr (OP == 2) return c < 0;
+    else if constexpr (OP == 3) return c <= 0;
+    else if constexpr (OP == 4) return c > 0;
+    else return c >= 0;
+}
+// ---- utf8 order core: end --------------------------------------------------
+
+// `utf8 column u <three-way> literal j` for the K rows of a tile whose offsets
+// are in s / nx (utf8_offs_tile) and NL literals (the two bounds of a prefix
+// range share one fetch of the rows' heads): -1 / 0 / 1 per row, plus one, in
+// two bits of res[j] each (one register per comparison). Every row's head
+// words (at most H / 4 + 1 aligned words, only words holding bytes of the
+// row) are in flight together before any is used; the literals' heads are
+// wave-uniform and built once. Rows past n_rows come out
+// as empty strings (the caller masks them). The literals' bytes `q` come from
+// the kernel's own Args.
+template <int BLOCK, int K, int H, int NL>
+__device__ __forceinline__ void utf8_cmp_lits_tile(const Args& A, int u, const int (&lit)[NL],
+                                                   const char* const (&q)[NL], const int (&s)[K], const int (&nx)[K],
+                                                   int lane, unsigned (&res)[NL]) {
+    static_assert(K <= 16 && NL >= 1 && NL * K <= 32, "two result bits per row; one pending bit per row and literal");
+    typedef typename Utf8Head<H>::W W;
+    const u8* by = A.bytes[u];
+    const unsigned bmis = (unsigned)((u64)by & 3u);  // sliced arrays and views misalign the base
+    const u8* ab = by - bmis;
+    int len[NL], hq[NL], hmax = 0;
+    W qh[NL];
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+        len[j] = A.str_len[lit[j]];
+        hq[j] = len[j] < H ? len[j] : H;
+        hmax = hq[j] > hmax ? hq[j] : hmax;
+        W ql = 0;
+#pragma unroll
+        for (int i = 0; i < H; ++i)
+            if (i < hq[j]) ql |= (W)(u8)q[j][i] << (8 * i);
+        qh[j] = utf8_bswap(ql);
+        res[j] = 0;
+    }
+    int L[K];  // (utf8_end moves data across lanes: every lane active, so not inside the rare path's branch)
+#pragma unroll
+    for (int k = 0; k < K; ++k) L[k] = utf8_end(s[k], nx[k], lane) - s[k];
+    W h[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) h[k] = utf8_head_window<W>(ab, (unsigned)s[k] + bmis, L[k] < hmax ? L[k] : hmax);
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int j = 0; j < NL; ++j)
+            res[j] |= (unsigned)(utf8_cmp_windowed<W>(h[k], qh[j], hq[j], L[k], len[j]) + 1) << (2 * k);
+    // the rare path, after the head words are dead: rows equal to a literal in their first H
+    // bytes. One copy of the walk, a lane's pending (literal, row) pairs one after the other
+    // (the row's offsets picked by compares: s / L stay in registers).
+    unsigned pend = 0;
+#pragma unroll
+    for (int j = 0; j < NL; ++j)
+#pragma unroll
+        for (int k = 0; k < K; ++k) pend |= (unsigned)(((res[j] >> (2 * k)) & 3u) == 3u) << (j * K + k);
+    while (pend) {
+        const int b = __builtin_ctz(pend);
+        pend &= pend - 1u;
+        const int jj = b / K, k = b % K;
+        int sk = 0, lk = 0, ln = len[0];
+        const char* qq = q[0];
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            sk = i == k ? s[i] : sk;
+            lk = i == k ? L[i] : lk;
+        }
+#pragma unroll
+        for (int j = 1; j < NL; ++j) {
+            qq = j == jj ? q[j] : qq;
+            ln = j == jj ? len[j] : ln;
+        }
+        const unsigned c = (unsigned)(utf8_cmp_tail(by + sk, lk, (const u8*)qq, ln, H) + 1) << (2 * k);
+#pragma unroll
+        for (int j = 0; j < NL; ++j)
+            if (j == jj) res[j] = (res[j] & ~(3u << (2 * k))) | c;
+    }
+}
+
+// One literal.
+template <int BLOCK, int K, int H>
+__device__ __forceinline__ void utf8_cmp_lit_tile(const Args& A, int u, int lit, const char* q, const int (&s)[K],
+                                                  const int (&nx)[K], int lane, unsigned& res) {
+    const int l_[1] = {lit};
+    const char* const q_[1] = {q};
+    unsigned r_[1];
+    utf8_cmp_lits_tile<BLOCK, K, H, 1>(A, u, l_, q_, s, nx, lane, r_);
+    res = r_[0];
+}
+
+// Row k's three-way result of utf8_cmp_lit_tile under the ordering operator OP.
+template <int OP>
+__device__ __forceinline__ bool utf8_ord_tile(unsigned res, int k) {
+    return utf8_ord<OP>((int)((res >> (2 * k)) & 3u) - 1);
+}
+
+// Per-row forms (projections, aggregate arguments and keys, kernels without
+// a tile pre-pass): `column u OP literal` and `column u OP column v`. Rows
+// past n_rows are not selected.
+template <int OP, int H>
+__device__ __forceinline__ bool utf8_cmp_lit(const Args& A, int u, i64 row, int lit, const char* q) {
+    if (row >= A.n_rows) return false;
+    const int s = A.offs[u][row], e = A.offs[u][row + 1];
+    return utf8_ord<OP>(utf8_cmp_bytes<H>(A.bytes[u] + s, e - s, (const u8*)q, A.str_len[lit]));
+}
+
+template <int OP, int H>
+__device__ __forceinline__ bool utf8_cmp_col(const Args& A, int u, int v, i64 row) {
+    if (row >= A.n_rows) return false;
+    const int s0 = A.offs[u][row], e0 = A.offs[u][row + 1];
+    const int s1 = A.offs[v][row], e1 = A.offs[v][row + 1];
+    return utf8_ord<OP>(utf8_cmp_bytes<H>(A.bytes[u] + s0, e0 - s0, A.bytes[v] + s1, e1 - s1));
+}
+
 __device__ __forceinline__ bool utf8_valid(const Args& A, int u, i64 row) {
     const u8* v = A.svalid[u];
     return !v || row >= A.n_rows || ((v[row >> 3] >> (row & 7)) & 1);

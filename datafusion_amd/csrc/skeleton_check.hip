@@ -31,6 +31,26 @@ extern "C" __global__ __launch_bounds__(512) void dfmi_skeleton_check(const dfmi
     bool eq2[K];
     dfmi::utf8_eq_lit_tile_reg<BLOCK, K, 4>(A, 0, 0, A.str + A.str_off[0], us, ue, lane, eq2);
     for (int k = 0; k < K; ++k) eq[k] = eq[k] || eq2[k];
+    // Utf8 ordering: the tile pre-pass at both head widths, the per-row forms
+    unsigned o4, o8;
+    dfmi::utf8_cmp_lit_tile<BLOCK, K, 4>(A, 0, 0, A.str + A.str_off[0], us, ue, lane, o4);
+    dfmi::utf8_cmp_lit_tile<BLOCK, K, 8>(A, 0, 1, A.str + A.str_off[1], us, ue, lane, o8);
+    {
+        const int l_[2] = {0, 1};
+        const char* const q_[2] = {A.str + A.str_off[0], A.str + A.str_off[1]};
+        unsigned r_[2];
+        dfmi::utf8_cmp_lits_tile<BLOCK, K, 8, 2>(A, 0, l_, q_, us, ue, lane, r_);
+        o4 ^= r_[0];
+        o8 ^= r_[1];
+    }
+    for (int k = 0; k < K; ++k) {
+        const i64 row = base + k * BLOCK + tid;
+        eq[k] = eq[k] || (dfmi::utf8_ord_tile<2>(o4, k) && dfmi::utf8_ord_tile<5>(o8, k)) ||
+                dfmi::cmp_opt<3>(dfmi::utf8_valid(A, 0, row), true,
+                                 dfmi::utf8_cmp_lit<3, 8>(A, 0, row, 0, A.str + A.str_off[0])) ||
+                dfmi::utf8_cmp_lit<4, 4>(A, 0, row, 1, A.str + A.str_off[1]) ||
+                dfmi::utf8_cmp_col<2, 8>(A, 0, 1, row) || dfmi::utf8_cmp_col<5, 4>(A, 0, 1, row);
+    }
     for (int k = 0; k < K; ++k) {
         selm |= (unsigned)eq[k] << k;
         wm[k] = __ballot((selm >> k) & 1);

@@ -256,7 +256,8 @@ class Literal(Expr):
         if v.dtype in (DataType.Float32, DataType.Float64):
             node["f64"] = float(v.value)
         elif v.dtype == DataType.Utf8:
-            node["str"] = v.value.encode("utf-8")
+            # (surrogateescape: a literal of arbitrary bytes, as program names decode them)
+            node["str"] = v.value.encode("utf-8", errors="surrogateescape")
         elif v.dtype == DataType.Boolean:
             node["i64"] = 1 if v.value else 0
         elif v.dtype != DataType.Null:

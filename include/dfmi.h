@@ -244,6 +244,33 @@ typedef struct dfmi_expr_node {
                                            value, no struct change: DFMI_ABI_VERSION
                                            stays 4 */
 
+#define DFMI_FLAG_EXT_UTF8_ORDER   0x100u
+/* With DFMI_FLAG_EXT_UTF8_COMPARE (alone it changes nothing): the ordering
+ * operators Lt, LtEq, Gt, GtEq over two Utf8 operands instead of the run-time
+ * ExecutionError("comparison_ops"). The planner already builds these plans
+ * (get_supertype(Utf8, Utf8) = Utf8); the reference executes no Utf8
+ * comparison, so the feature is build-defined, parity unpinned.
+ *   operands: column-literal, literal-column, column-column, and
+ *             literal-literal (folded when the kernel is generated); mixed
+ *             types (Utf8 against Float64, ...) stay "comparison_ops";
+ *   result:   a non-null Boolean;
+ *   order:    the two byte strings as sequences of unsigned bytes -- the
+ *             first differing byte decides, a proper prefix is less (Rust's
+ *             [u8] / str order, the GROUP BY / ORDER BY key order). 0x00 and
+ *             0x80-0xFF are ordinary bytes, invalid UTF-8 included:
+ *             "a" < "a\0", "a\x7f" < "a\x80";
+ *   nulls:    as the numeric comparisons (arrow's cmp_opt): never a null
+ *             result, a null is less than every value, null against null as
+ *             there (Lt / LtEq true, Gt / GtEq false). After a Selection the
+ *             columns are all-valid and a null slot compares by its raw
+ *             bytes, as Utf8 = does;
+ *   errors:   none of its own; its operands' ordinals come before its own;
+ *   limits:   8 string literals and 256 literal bytes per kernel, as for =.
+ * It runs wherever Utf8 = runs (predicates, Boolean projections, aggregate
+ * arguments, GROUP BY / ORDER BY key expressions; every batch form). Without
+ * both flags every expression compiles and fails exactly as before. One flag
+ * bit, no struct change, no new entry point: DFMI_ABI_VERSION stays 4. */
+
 /* Signature of a built-in scalar function, for a binding's
  * SchemaProvider::get_function_meta (sqlplanner.rs:330-350 casts each
  * argument to arg_types[i]). Returns 0 and fills *num_args, *return_type and
