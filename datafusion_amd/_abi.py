@@ -36,6 +36,7 @@ DFMI_FLAG_EXT_SORT = 0x20
 DFMI_FLAG_EXT_SCALAR_FUNCTIONS = 0x40
 DFMI_FLAG_EXT_AGG_AVG = 0x80
 DFMI_FLAG_EXT_UTF8_ORDER = 0x100  # with DFMI_FLAG_EXT_UTF8_COMPARE: Utf8 <, <=, >, >=
+DFMI_FLAG_EXT_AGG_MINMAX_ANY = 0x200  # with DFMI_FLAG_EXT_AGGREGATE: MIN / MAX over a Boolean or Utf8 argument
 
 # dfmi_agg_fn (AggregateType, expression.rs:33-40)
 DFMI_AGG_MIN = 0
@@ -187,6 +188,7 @@ EXPORTED = [
     "dfmi_agg_state_finish_grouped",
     "dfmi_agg_state_group_keys_utf8",
     "dfmi_agg_state_group_keys_utf8_part",
+    "dfmi_agg_state_value_bytes",
     "dfmi_agg_state_grouped_partial_bytes",
     "dfmi_agg_state_grouped_partial",
     "dfmi_agg_merge_grouped_partials",
@@ -384,6 +386,9 @@ def lib() -> C.CDLL:
     L.dfmi_agg_state_group_keys_utf8_part.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                                       C.c_int64, P(C.c_int64), P(dfmi_error)]
     L.dfmi_agg_state_group_keys_utf8_part.restype = C.c_int32
+    L.dfmi_agg_state_value_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_int64, C.POINTER(C.c_int64), C.POINTER(dfmi_error)]
+    L.dfmi_agg_state_value_bytes.restype = C.c_int32
     L.dfmi_agg_merge_grouped_partials_keys_utf8.argtypes = [P(C.c_void_p), C.c_int32, P(C.c_void_p), P(C.c_int64),
                                                             C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                                             C.c_int64, P(C.c_int64), P(dfmi_error)]

@@ -56,7 +56,7 @@ HashDev& hashdev(dfmi_context* ctx, dfmi_agg_state* st) {
     int w = 1;  // word 0: the group's rows
     for (size_t j = 0; j < n; ++j) {
         H->off.push_back(w);
-        const bool fs = acc_fn(st->aggs[j]->fn) == DFMI_AGG_SUM && is_float_type(st->aggs[j]->arg.type);
+        const bool fs = acc_fn(*st->aggs[j]) == DFMI_AGG_SUM && is_float_type(st->aggs[j]->arg.type);
         if (fs) H->foff.push_back(w + 4);
         w += 4 + (fs ? kAggLimbs : 0);
     }
@@ -206,7 +206,7 @@ void host_merge_rows(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<df
         }
     }
     auto valid = [&](size_t o, int64_t i) { return hb[o].empty() || ((hb[o][i >> 3] >> (i & 7)) & 1); };
-    std::vector<std::vector<Partial>*> touched;
+    std::vector<GroupState*> touched;
     std::string enc;
     const int64_t cnt = rows ? (int64_t)rows->size() : m;
     for (int64_t x = 0; x < cnt; ++x) {
@@ -230,7 +230,7 @@ void host_merge_rows(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<df
             }
             encode_part(enc, k);
         }
-        std::vector<Partial>* entry;
+        GroupState* entry;
         auto ix = st->index.find(enc);
         if (ix != st->index.end()) {
             entry = ix->second;
@@ -238,16 +238,23 @@ void host_merge_rows(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<df
             entry = &group_entry(st->groups, std::move(hk), n);
             st->index.emplace(enc, entry);
         }
-        std::vector<Partial>& g = *entry;
+        GroupState& g = *entry;
         if (g[n].flags == 0) {  // first touch in this call: normalise it at the end
             g[n].flags = 1;
             touched.push_back(entry);
         }
         ++g[n].count;  // the group's selected rows
         for (size_t j = 0; j < n; ++j)
-            if (valid(nk + j, i)) host_accumulate(g[j], acc_fn(st->aggs[j]->fn), cols[nk + j].type, hv[nk + j].data(), i);
+            if (valid(nk + j, i)) {
+                host_accumulate(g[j], acc_fn(*st->aggs[j]), cols[nk + j].type, hv[nk + j].data(), i);
+                if (is_utf8_extreme(*st->aggs[j])) {  // the same comparator as the device's candidate pass
+                    if (g.str.size() < n) g.str.resize(n);
+                    str_offer(g.str[j], st->aggs[j]->fn == DFMI_AGG_MIN, hv[nk + j].data() + ho[nk + j][i],
+                              (size_t)(ho[nk + j][i + 1] - ho[nk + j][i]));
+                }
+            }
     }
-    for (std::vector<Partial>* e : touched) {  // only the entries this call touched
+    for (GroupState* e : touched) {  // only the entries this call touched
         for (Partial& q : *e) normalize(q);
         (*e)[n].flags = 0;
     }
@@ -338,7 +345,7 @@ void accumulate_bucketed(dfmi_context* ctx, dfmi_agg_state* st, HashDev& H, cons
         sa.arg[j] = c;
         nullable = nullable || c.validity;
         ba.a[j].c = c;
-        ba.a[j].fn = acc_fn(st->aggs[j]->fn);
+        ba.a[j].fn = acc_fn(*st->aggs[j]);
         ba.a[j].off = H.off[j];
         ba.pcol[j] = -1;
         const bool needs = st->aggs[j]->fn != DFMI_AGG_COUNT && c.type != DFMI_TYPE_UTF8 && c.type != DFMI_TYPE_BOOLEAN;
@@ -520,7 +527,7 @@ void group_batches_hashed(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_prog
 // The m evaluated rows of `cols` (keys, then arguments: one batch's, or a
 // coalesced call's packed segments) through the table: claim with growth and
 // rerun, record and arena growth, normalisation, accumulate, the collision list.
-void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<dfmi::gb::Col>& cols, int64_t m,
+void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<dfmi::gb::Col>& evaluated, int64_t m,
                        const AggDiag& diag, std::chrono::steady_clock::time_point t0) {
     HashDev& H = hashdev(ctx, st);
     const bool prof = diag.finish_profile;
@@ -529,6 +536,18 @@ void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<
     if (m > 0x7fffffffll) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "GROUP BY batch of 2^31 selected rows or more"};
     const size_t nk = st->keys.size(), n = st->aggs.size();
     hipStream_t stream = ctx->stream;
+    // a Boolean MIN / MAX is an integer extreme over 0 / 1: its bitmap expanded to a
+    // UInt8 column, which every pass below (and the host merge) takes as it is
+    std::vector<dfmi::gb::Col> cols = evaluated;
+    for (size_t j = 0; j < n; ++j) {
+        dfmi::gb::Col& c = cols[nk + j];
+        if (c.type != DFMI_TYPE_BOOLEAN || st->aggs[j]->fn == DFMI_AGG_COUNT) continue;
+        uint8_t* u8 = (uint8_t*)H.bufs[HashDev::BoolArg + j].reserve((size_t)(m + 7) / 8 * 8);
+        HIP_TRY(dfmi::gb::launch_bits_to_u8((const uint8_t*)c.values, u8, m, stream));
+        c.type = DFMI_TYPE_UINT8;
+        c.width = 1;
+        c.values = u8;
+    }
     if (H.rows_cap < m) {
         H.rows_cap = 0;
         const int64_t want = m + m / 4;
@@ -579,6 +598,8 @@ void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<
         H.rows_since_norm = 0;
     }
     HIP_TRY(hipMemsetAsync(&H.dhdr()->collided, 0, 8, stream));
+    // (a state with Utf8 MIN / MAX aggregates keeps the rows' group ids for the string passes)
+    unsigned* rg = st->sx ? (unsigned*)H.bufs[HashDev::BucketRowGroup].reserve((size_t)m * 4) : nullptr;
     if (use_buckets(st, H, m, ng, diag)) {
         accumulate_bucketed(ctx, st, H, cols, m, ng, ca.epoch);
     } else {
@@ -593,7 +614,7 @@ void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<
         aa.sidx = H.sidx.as<int32_t>();
         for (size_t j = 0; j < n; ++j) {
             aa.a[j].c = cols[nk + j];
-            aa.a[j].fn = acc_fn(st->aggs[j]->fn);
+            aa.a[j].fn = acc_fn(*st->aggs[j]);
             aa.a[j].off = H.off[j];
         }
         aa.naggs = (int)n;
@@ -601,7 +622,18 @@ void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<
         aa.acc = H.records();
         aa.hdr = H.dhdr();
         aa.coll_rows = H.coll.as<int32_t>();
+        aa.rg = rg;
         HIP_TRY(dfmi::gb::launch_accumulate(aa, stream));
+    }
+    // Utf8 MIN / MAX: the strings of the rows added on the device (the listed rows' go with the host merge below)
+    // (the records have counted the batch: a failure of the string passes fails the query)
+    H.ngroups = ng;
+    try {
+        strext_batch(ctx, st, cols.data() + nk, rg, m, ng);
+    } catch (const Fail& f) {
+        st->failed = true;
+        set_err(&st->failure, f.code, f.msg);
+        throw;
     }
     read_hdr(ctx, H);
     if (prof) {
@@ -652,7 +684,7 @@ const unsigned long long* round_records(dfmi_context* ctx, const dfmi_agg_state*
         ra.off[j] = H.off[j];
         const int t = st->aggs[j]->arg.type;
         const int fn = st->aggs[j]->fn;
-        ra.kind[j] = acc_fn(fn) == DFMI_AGG_SUM && is_float_type(t)
+        ra.kind[j] = acc_fn(*st->aggs[j]) == DFMI_AGG_SUM && is_float_type(t)
                          ? (t == DFMI_TYPE_FLOAT32 ? 2 : 1) + (fn == DFMI_AGG_AVG ? 2 : 0)
                          : 0;
     }
@@ -698,8 +730,10 @@ void read_table(dfmi_context* ctx, dfmi_agg_state* st, FlatGroups& f, bool round
     read_hdr(ctx, H);  // (synchronises the stream)
     f.arena.resize((size_t)H.hh.p->arena_end);
     if (H.hh.p->arena_end) HIP_TRY(hipMemcpy(f.arena.data(), H.arena.as<uint8_t>(), H.hh.p->arena_end, hipMemcpyDeviceToHost));
+    strext_read(ctx, st, f, ng);
     if (rounded) return;
     reset_table(ctx, H);  // for the next batch
+    strext_reset(ctx, st);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
 }
 
@@ -860,7 +894,7 @@ void sort_flat(const dfmi_agg_state* st, FlatGroups& f) {
 // groupby.h; word 0 the group's rows).
 void rec_partial(const dfmi_agg_state* st, const FlatGroups& f, const uint64_t* rec, size_t j, Partial& q) {
     const uint64_t* w = rec + f.off[j];
-    const int fn = acc_fn(st->aggs[j]->fn);
+    const int fn = acc_fn(*st->aggs[j]);
     q.count = rec[0] - w[0];  // the group's rows minus its NULL arguments
     if (fn == DFMI_AGG_SUM && is_float_type(st->aggs[j]->arg.type)) {
         q.flags = (w[1] & 0xffffffffull) | (q.count > w[3] ? AGGF_NONNEGZERO : 0);
@@ -893,11 +927,18 @@ void materialize_flat(dfmi_agg_state* st, FlatGroups& f) {
             else k = fixed_part(kt, f.kw[g * nk + p]);
         }
         const uint64_t* rec = &f.acc[(size_t)g * f.words];
-        std::vector<Partial> parts(n + 1);
+        GroupState parts(n + 1);
         parts[n].count = rec[0];
         for (size_t j = 0; j < n; ++j) rec_partial(st, f, rec, j, parts[j]);
-        if (fresh) st->groups.emplace_hint(st->groups.end(), std::move(hk), std::move(parts));
-        else merge_group(group_entry(st->groups, std::move(hk), n), parts, st->aggs.data(), n);
+        if (st->sx) {
+            parts.str.resize(n);
+            for (size_t x = 0; x < st->sx->x.size(); ++x) parts.str[st->sx->x[x].agg] = strext_flat_value(f, x, g);
+        }
+        if (fresh) {
+            st->groups.emplace_hint(st->groups.end(), std::move(hk), std::move(parts));
+        } else {
+            merge_group(group_entry(st->groups, std::move(hk), n), parts, st->aggs.data(), n);
+        }
     }
 }
 
@@ -980,7 +1021,7 @@ bool finish_device(dfmi_context* ctx, dfmi_agg_state* st, const AggDiag& diag, i
     if (st->keys.size() != 1 || st->keys[0].type == DFMI_TYPE_UTF8 || !st->hd ||
         st->aggs.size() > (size_t)dfmi::gb::kMaxAggs)
         return false;
-    if (diag.host_finish) return false;
+    if (diag.host_finish || st->sx) return false;  // (a Utf8 MIN / MAX's bytes are joined on the host)
     const char* force = diag.device_emit;
     if (force && !atoi(force)) return false;
     if (!st->groups.empty() || (st->flat && !st->flat->rounded)) return false;
@@ -1033,6 +1074,9 @@ void emit_flat(const dfmi_agg_state* st, const FlatGroups& f, int64_t cap, dfmi_
     if (*num_groups > cap) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "group capacity too small"};
     if (*num_groups > 0 && (!keys || !values)) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
     const size_t nk = f.nk, n = st->aggs.size();
+    std::vector<int> xof(n, -1);  // aggregate j's index among the Utf8 MIN / MAX aggregates
+    if (st->sx)
+        for (size_t x = 0; x < st->sx->x.size(); ++x) xof[st->sx->x[x].agg] = (int)x;
     auto emit_range = [&](uint64_t i0, uint64_t i1) {
         Partial q;
         for (uint64_t i = i0; i < i1; ++i) {
@@ -1051,7 +1095,7 @@ void emit_flat(const dfmi_agg_state* st, const FlatGroups& f, int64_t cap, dfmi_
             for (size_t j = 0; j < n; ++j) {
                 q.flags = q.key = q.isum = 0;  // (rec_partial sets count and, for a float SUM, every digit)
                 rec_partial(st, f, rec, j, q);
-                if (f.rounded && acc_fn(st->aggs[j]->fn) == DFMI_AGG_SUM && is_float_type(st->aggs[j]->arg.type)) {
+                if (f.rounded && acc_fn(*st->aggs[j]) == DFMI_AGG_SUM && is_float_type(st->aggs[j]->arg.type)) {
                     const uint64_t* w = rec + f.off[j];
                     Rounded r;
                     memcpy(&r.v, &w[2], 8);
@@ -1059,6 +1103,10 @@ void emit_flat(const dfmi_agg_state* st, const FlatGroups& f, int64_t cap, dfmi_
                     values[i * n + j] = finish_normalized(*st->aggs[j], q, &r);
                 } else {
                     values[i * n + j] = finish_normalized(*st->aggs[j], q);
+                    if (xof[j] >= 0 && !values[i * n + j].is_null) {  // the value's byte length
+                        const dfmi::sx::Ent& e = f.sx_ent[(size_t)xof[j]][g];
+                        values[i * n + j].bits = e.len == dfmi::sx::kNone ? 0 : e.len;
+                    }
                 }
             }
         }

@@ -30,6 +30,34 @@ static int agg_fn_of(const std::string& name, uint32_t flags) {
     return -1;
 }
 
+bool is_utf8_extreme(const dfmi_aggregate& a) {
+    return (a.fn == DFMI_AGG_MIN || a.fn == DFMI_AGG_MAX) && a.arg.type == DFMI_TYPE_UTF8;
+}
+
+int acc_fn(const dfmi_aggregate& a) { return is_utf8_extreme(a) ? (int)DFMI_AGG_COUNT : acc_fn(a.fn); }
+
+bool any_utf8_extreme(const dfmi_aggregate* const* aggs, size_t n) {
+    for (size_t j = 0; j < n; ++j)
+        if (aggs[j] && is_utf8_extreme(*aggs[j])) return true;
+    return false;
+}
+
+int utf8_compare(const uint8_t* a, size_t la, const uint8_t* b, size_t lb) {
+    const size_t n = std::min(la, lb);
+    for (size_t i = 0; i < n; ++i)
+        if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
+    return la == lb ? 0 : (la < lb ? -1 : 1);
+}
+
+void str_offer(StrVal& v, bool is_min, const uint8_t* s, size_t len) {
+    if (v.has) {
+        const int c = utf8_compare(s, len, (const uint8_t*)v.s.data(), v.s.size());
+        if (is_min ? c >= 0 : c <= 0) return;
+    }
+    v.has = true;
+    v.s.assign((const char*)s, len);
+}
+
 bool is_float_type(int t) { return t == DFMI_TYPE_FLOAT32 || t == DFMI_TYPE_FLOAT64; }
 
 bool is_signed_type(int t) {
@@ -189,6 +217,7 @@ dfmi_agg_value finish_normalized(const dfmi_aggregate& a, const Partial& p, cons
         r.is_null = 1;
         return r;
     }
+    if (t == DFMI_TYPE_UTF8) return r;  // a Utf8 MIN / MAX: its caller sets bits, the value's byte length
     const bool f32 = t == DFMI_TYPE_FLOAT32;
     const uint64_t qnan = f32 ? 0x7FC00000ull : 0x7FF8000000000000ull;
     if (a.fn == DFMI_AGG_SUM || a.fn == DFMI_AGG_AVG) {  // (an AVG's argument is a float: dfmi_compile_aggregate)
@@ -242,16 +271,23 @@ static void merge_partial(Partial& into, const Partial& p, bool is_min) {
 }
 
 // The group entry of key `hk` (created with n + 1 empty partials).
-std::vector<Partial>& group_entry(GroupMap& groups, HKey&& hk, size_t n) {
+GroupState& group_entry(GroupMap& groups, HKey&& hk, size_t n) {
     auto it = groups.find(hk);
-    if (it == groups.end()) it = groups.emplace(std::move(hk), std::vector<Partial>(n + 1)).first;
+    if (it == groups.end()) it = groups.emplace(std::move(hk), GroupState(n + 1)).first;
     return it->second;
 }
 
-void merge_group(std::vector<Partial>& into, const std::vector<Partial>& parts, const dfmi_aggregate* const* aggs,
-                 size_t n) {
+// One group's state merged into another's: the partials, the hidden row count
+// and the Utf8 extremes beside them (one function, so that no merge site can
+// take the partials and leave the strings behind).
+void merge_group(GroupState& into, const GroupState& parts, const dfmi_aggregate* const* aggs, size_t n) {
     for (size_t j = 0; j < n; ++j) merge_partial(into[j], parts[j], aggs[j]->fn == DFMI_AGG_MIN);
     into[n].count += parts[n].count;  // the hidden count: the group's selected rows
+    if (parts.str.empty()) return;
+    if (into.str.size() < n) into.str.resize(n);
+    for (size_t j = 0; j < n && j < parts.str.size(); ++j)
+        if (parts.str[j].has && is_utf8_extreme(*aggs[j]))
+            str_offer(into.str[j], aggs[j]->fn == DFMI_AGG_MIN, (const uint8_t*)parts.str[j].s.data(), parts.str[j].s.size());
 }
 
 KeyPart fixed_part(int kt, uint64_t bits) {
@@ -345,7 +381,9 @@ void host_accumulate(Partial& p, int fn, int t, const uint8_t* vals, int64_t i) 
         case DFMI_TYPE_UINT64: return host_accumulate_t(p, fn, ((const uint64_t*)vals)[i]);
         case DFMI_TYPE_FLOAT32: return host_accumulate_t(p, fn, ((const float*)vals)[i]);
         case DFMI_TYPE_FLOAT64: return host_accumulate_t(p, fn, ((const double*)vals)[i]);
-        default: ++p.count;  // COUNT of a Boolean / Utf8 argument: non-null values only
+        case DFMI_TYPE_BOOLEAN:  // a bitmap: COUNT, or MIN / MAX over 0 / 1 (DFMI_FLAG_EXT_AGG_MINMAX_ANY)
+            return host_accumulate_t(p, fn == DFMI_AGG_SUM ? (int)DFMI_AGG_COUNT : fn, (uint8_t)((vals[i >> 3] >> (i & 7)) & 1));
+        default: ++p.count;  // COUNT of a Utf8 argument: non-null values only
     }
 }
 
@@ -368,7 +406,11 @@ void emit_groups(const GroupMap& groups, const std::vector<int>& ktypes, const d
             k.bits = kp.null || kt == DFMI_TYPE_UTF8 ? 0 : (kt == DFMI_TYPE_BOOLEAN ? kp.bits : narrow_int(kp.bits, kt));
             k.count = (int64_t)v[n].count;  // the group's selected rows
         }
-        for (size_t j = 0; j < n; ++j) values[g * n + j] = finish_one(*aggs[j], v[j]);
+        for (size_t j = 0; j < n; ++j) {
+            dfmi_agg_value& out = values[g * n + j];
+            out = finish_one(*aggs[j], v[j]);
+            if (is_utf8_extreme(*aggs[j]) && !out.is_null) out.bits = j < v.str.size() ? v.str[j].s.size() : 0;
+        }
         ++g;
     }
 }
@@ -391,6 +433,36 @@ void emit_key_bytes(const GroupMap& groups, int part, int32_t* offsets, int64_t 
         pos += (int64_t)s.size();
         offsets[++g] = (int32_t)pos;
     }
+}
+
+void emit_value_bytes(const std::vector<StrVal>& vals, int32_t* offsets, int64_t num_offsets, uint8_t* data,
+                      int64_t data_capacity, int64_t* data_length) {
+    int64_t total = 0;
+    for (const StrVal& v : vals) total += v.has ? (int64_t)v.s.size() : 0;
+    *data_length = total;
+    if (total > 0x7fffffffll) throw Fail{DFMI_ERR_CAPACITY, "Utf8 aggregate values of 2^31 bytes or more"};
+    if (num_offsets < (int64_t)vals.size() + 1 || data_capacity < total)
+        throw Fail{DFMI_ERR_CAPACITY, "value offsets / bytes capacity too small"};
+    if (!offsets || (total && !data)) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
+    int64_t g = 0, pos = 0;
+    offsets[0] = 0;
+    for (const StrVal& v : vals) {
+        if (v.has && !v.s.empty()) {
+            memcpy(data + pos, v.s.data(), v.s.size());
+            pos += (int64_t)v.s.size();
+        }
+        offsets[++g] = (int32_t)pos;
+    }
+}
+
+// The values of Utf8 MIN / MAX `agg` of `groups`, in order, as a BinaryArray (a null value's slot empty).
+void emit_value_bytes(const GroupMap& groups, int agg, int32_t* offsets, int64_t num_offsets, uint8_t* data,
+                      int64_t data_capacity, int64_t* data_length) {
+    std::vector<StrVal> vals;
+    vals.reserve(groups.size());
+    for (const auto& kv : groups)
+        vals.push_back((size_t)agg < kv.second.str.size() && kv.second[(size_t)agg].count ? kv.second.str[(size_t)agg] : StrVal{});
+    emit_value_bytes(vals, offsets, num_offsets, data, data_capacity, data_length);
 }
 
 // Serialised per-group partials (multi-GPU GROUP BY): a header, then per group
@@ -473,7 +545,7 @@ void merge_serialized(GroupMap& groups, std::vector<int>& ktypes, const dfmi_agg
                 p += pad;
             }
             if ((size_t)(end - p) < (n + 1) * sizeof(Partial)) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "bad grouped partial"};
-            std::vector<Partial> parts(n + 1);
+            GroupState parts(n + 1);
             memcpy(parts.data(), p, (n + 1) * sizeof(Partial));
             p += (n + 1) * sizeof(Partial);
             merge_group(group_entry(groups, std::move(hk), n), parts, aggs, n);
@@ -498,7 +570,14 @@ extern "C" int32_t dfmi_compile_aggregate(const char* name, const dfmi_program* 
         if (fn < 0) throw Fail{DFMI_ERR_PANIC, std::string("not yet implemented: Unsupported aggregate function '") + name + "'"};
         const int want = fn == DFMI_AGG_COUNT ? DFMI_TYPE_UINT64 : arg->type;  // sqlplanner.rs:296-330
         if (return_type != want) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "aggregate return type does not match the planner's"};
-        if (fn != DFMI_AGG_COUNT && !is_numeric_type(arg->type))
+        // DFMI_FLAG_EXT_AGG_MINMAX_ANY: MIN / MAX of a Boolean argument (false < true), kept as an
+        // integer extreme over 0 / 1 -- the partial and the wire format are an integer MIN / MAX's
+        const bool bool_extreme = (flags & DFMI_FLAG_EXT_AGG_MINMAX_ANY) && arg->type == DFMI_TYPE_BOOLEAN &&
+                                  (fn == DFMI_AGG_MIN || fn == DFMI_AGG_MAX);
+        // ... and of a Utf8 argument: bytewise order, inside the record machinery a COUNT (agg_host.h acc_fn)
+        const bool utf8_extreme = (flags & DFMI_FLAG_EXT_AGG_MINMAX_ANY) && arg->type == DFMI_TYPE_UTF8 &&
+                                  (fn == DFMI_AGG_MIN || fn == DFMI_AGG_MAX);
+        if (fn != DFMI_AGG_COUNT && !is_numeric_type(arg->type) && !bool_extreme && !utf8_extreme)
             throw Fail{DFMI_ERR_NOT_IMPLEMENTED, std::string("aggregate over ") + type_debug(arg->type)};
         // the state keeps only a wrapping 64-bit integer sum: no exact sum to divide
         if (fn == DFMI_AGG_AVG && !is_float_type(arg->type))
@@ -525,6 +604,7 @@ extern "C" int32_t dfmi_agg_merge_grouped_partials(const dfmi_aggregate* const* 
     return guarded(err, [&]() -> int32_t {
         if (!aggs || n <= 0 || !partials || !sizes || nparts <= 0 || !num_groups)
             throw Fail{DFMI_ERR_INVALID_ARGUMENT, "bad argument"};
+        if (any_utf8_extreme(aggs, (size_t)n)) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, kUtf8ExtremePartial};
         GroupMap groups;
         std::vector<int> kt;
         merge_serialized(groups, kt, aggs, (size_t)n, partials, sizes, nparts);
@@ -541,6 +621,7 @@ extern "C" int32_t dfmi_agg_merge_grouped_partials_keys_utf8(const dfmi_aggregat
     return guarded(err, [&]() -> int32_t {
         if (!aggs || n <= 0 || !partials || !sizes || nparts <= 0 || !data_length)
             throw Fail{DFMI_ERR_INVALID_ARGUMENT, "bad argument"};
+        if (any_utf8_extreme(aggs, (size_t)n)) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, kUtf8ExtremePartial};
         GroupMap groups;
         std::vector<int> kt;
         merge_serialized(groups, kt, aggs, (size_t)n, partials, sizes, nparts);
@@ -555,6 +636,7 @@ extern "C" int32_t dfmi_agg_merge_partials(const dfmi_aggregate* const* aggs, in
                                            int32_t nparts, dfmi_agg_value* out, dfmi_error* err) {
     return guarded(err, [&]() -> int32_t {
         if (!aggs || n <= 0 || !partials || nparts <= 0 || !out) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "bad argument"};
+        if (any_utf8_extreme(aggs, (size_t)n)) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, kUtf8ExtremePartial};
         for (int j = 0; j < n; ++j) {
             Partial m;
             for (int r = 0; r < nparts; ++r) {

@@ -58,7 +58,21 @@ struct HKey {
         return false;
     }
 };
-using GroupMap = std::map<HKey, std::vector<Partial>>;  // key -> partials + the group's row count
+// A Utf8 MIN / MAX's extreme string on the host (none yet: !has). The bytes
+// travel beside the Partial, which the wire format copies with memcpy and
+// which therefore stays trivially copyable.
+struct StrVal {
+    bool has = false;
+    std::string s;
+};
+// A group's partials (+ its row count) and, beside them, the extreme of each
+// Utf8 MIN / MAX (str[j], sized on first use; empty without one).
+struct GroupState : std::vector<Partial> {
+    using std::vector<Partial>::vector;
+    explicit GroupState(std::vector<Partial>&& v) : std::vector<Partial>(std::move(v)) {}
+    std::vector<StrVal> str;
+};
+using GroupMap = std::map<HKey, GroupState>;  // key -> partials + the group's row count
 
 // A floating-point SUM already rounded (the device finish, k_group_round).
 struct Rounded {
@@ -71,6 +85,20 @@ struct Rounded {
 // generated sources and their cache keys see SUM, so SUM(e) and AVG(e) share
 // one code object.
 inline int acc_fn(int fn) { return fn == DFMI_AGG_AVG ? DFMI_AGG_SUM : fn; }
+// ... and a MIN / MAX over a Utf8 argument (DFMI_FLAG_EXT_AGG_MINMAX_ANY)
+// accumulates as COUNT: the record machinery tracks its count / null and
+// shares COUNT's code objects; the strings live beside it (str_extreme.h on
+// the device, GroupState::str on the host) and the finish joins the two.
+// (the wire format ranks exchange carries no string: every partial entry point refuses one)
+constexpr const char* kUtf8ExtremePartial = "partial state of a Utf8 MIN / MAX aggregate";
+bool is_utf8_extreme(const dfmi_aggregate& a);
+int acc_fn(const dfmi_aggregate& a);
+bool any_utf8_extreme(const dfmi_aggregate* const* aggs, size_t n);
+// < 0, 0, > 0: two byte strings as sequences of unsigned bytes, the first
+// differing byte decides, a proper prefix is less (the GROUP BY / ORDER BY order).
+int utf8_compare(const uint8_t* a, size_t la, const uint8_t* b, size_t lb);
+// One value offered to an extreme (is_min: keeps the lesser).
+void str_offer(StrVal& v, bool is_min, const uint8_t* s, size_t len);
 
 bool is_float_type(int t);
 bool is_signed_type(int t);
@@ -84,9 +112,13 @@ dfmi_agg_value finish_one(const dfmi_aggregate& a, Partial p);
 void host_accumulate(Partial& p, int fn, int t, const uint8_t* vals, int64_t i);
 
 KeyPart fixed_part(int kt, uint64_t bits);
-std::vector<Partial>& group_entry(GroupMap& groups, HKey&& hk, size_t n);
-void merge_group(std::vector<Partial>& into, const std::vector<Partial>& parts, const dfmi_aggregate* const* aggs,
-                 size_t n);
+GroupState& group_entry(GroupMap& groups, HKey&& hk, size_t n);
+void emit_value_bytes(const GroupMap& groups, int agg, int32_t* offsets, int64_t num_offsets, uint8_t* data,
+                      int64_t data_capacity, int64_t* data_length);
+// The same from values in output order (null: !has).
+void emit_value_bytes(const std::vector<StrVal>& vals, int32_t* offsets, int64_t num_offsets, uint8_t* data,
+                      int64_t data_capacity, int64_t* data_length);
+void merge_group(GroupState& into, const GroupState& parts, const dfmi_aggregate* const* aggs, size_t n);
 void emit_groups(const GroupMap& groups, const std::vector<int>& ktypes, const dfmi_aggregate* const* aggs, size_t n,
                  int64_t cap, dfmi_agg_value* keys, dfmi_agg_value* values, int64_t* num_groups);
 void emit_key_bytes(const GroupMap& groups, int part, int32_t* offsets, int64_t num_offsets, uint8_t* data,

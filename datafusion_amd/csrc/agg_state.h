@@ -11,6 +11,7 @@
 #include "agg_host.h"
 #include "exec_internal.h"
 #include "groupby.h"
+#include "str_extreme.h"
 
 namespace dfmi {
 namespace agg {
@@ -32,7 +33,8 @@ struct HashDev {
         // a coalesced call: the evaluation pass's per-batch segments packed dense, two per output column
         // (values, validity); the pack kernel's source table, jobs and prefix
         PackOut, PackTable = PackOut + 2 * (dfmi::gb::kMaxKeys + dfmi::gb::kMaxAggs),
-        kSlots
+        // accumulate_hashed: the argument of a Boolean MIN / MAX as UInt8 0 / 1, one per aggregate
+        BoolArg, kSlots = BoolArg + dfmi::gb::kMaxAggs
     };
     DevBuf ctl, slot;                 // the table's storage; `t` views it
     dfmi::gb::Table t{};
@@ -73,6 +75,29 @@ struct FlatGroups {
     HostBuf<unsigned> knull, klen;
     HostBuf<uint64_t> kw, acc;
     HostBuf<uint8_t> arena;
+    // a state with Utf8 MIN / MAX aggregates: per extreme (StrExt::x order) the groups' persisted winners, and their arena
+    std::vector<std::vector<dfmi::sx::Ent>> sx_ent;
+    std::vector<uint8_t> sx_arena;
+};
+
+// The Utf8 MIN / MAX aggregates of a state (str_extreme.h): per extreme the
+// side arrays over the dense group ids (one group when ungrouped), the
+// string arena they share, and the ungrouped evaluation pass's buffers.
+struct StrExt {
+    struct One {
+        int agg = 0;  // index among the state's aggregates
+        bool is_min = false;
+        DevBuf pref, best, ent;
+    };
+    std::vector<One> x;
+    uint64_t gcap = 0;  // groups the side arrays hold (initialised)
+    DevBuf arena, hdr;
+    uint64_t arena_cap = 0;
+    uint64_t arena_end = 0;  // the device counters after the last batch: bytes reserved,
+    uint64_t live = 0;       // bytes of the persisted winners
+    std::vector<DevBuf> eval;  // ungrouped: the evaluated argument columns (offsets, bytes, validity each)
+    std::vector<dfmi::aggh::StrVal> one;  // ungrouped: the last finish's values, by aggregate
+    bool finished = false;                // a finish has produced values (dfmi_agg_state_value_bytes)
 };
 
 }  // namespace agg
@@ -97,11 +122,12 @@ struct dfmi_agg_state {
     dfmi::aggh::GroupMap groups;  // merged groups (window flushes, hash-table drains, host merges)
     // the host merge's per-row lookup: encoded key -> entry of `groups` (map
     // nodes do not move), cleared with it
-    std::unordered_map<std::string, std::vector<dfmi::aggh::Partial>*> index;
+    std::unordered_map<std::string, dfmi::aggh::GroupState*> index;
     std::shared_ptr<dfmi::aggh::GroupMap> shown;  // groups dfmi_shard_agg_finish_grouped merged (else `groups`)
     std::unique_ptr<dfmi::agg::HashDev> hd;       // device hash table (created on first use)
     std::unique_ptr<dfmi::agg::FlatGroups> flat;  // a finish's groups, not yet in `groups` (finish_flat)
     std::unique_ptr<dfmi::agg::FlatGroups> spare_flat;  // a used one, its pinned buffers kept for the next drain
+    std::unique_ptr<dfmi::agg::StrExt> sx;  // Utf8 MIN / MAX aggregates (null: none)
     // integer keys: the per-batch key window comes from MIN / MAX of the key
     // over the batch's selected rows (a pre-pass through this same extension)
     dfmi_aggregate* mm[2] = {nullptr, nullptr};
@@ -191,6 +217,21 @@ void emit_flat(const dfmi_agg_state* st, const FlatGroups& f, int64_t cap, dfmi_
 void emit_key_bytes_flat(const FlatGroups& f, int part, int32_t* offsets, int64_t num_offsets, uint8_t* data,
                          int64_t data_capacity, int64_t* data_length);
 long bucketed_batches();
+
+// ---- agg_strext.cpp: the Utf8 MIN / MAX side structure's driver
+void strext_create(dfmi_context* ctx, dfmi_agg_state* st);  // st->sx when the state holds a Utf8 extreme
+// one batch's m evaluated rows: cols[j] the argument column of aggregate j (only the Utf8 extremes' are read),
+// rg the rows' dense group ids (null: one group), ngroups the groups the device holds
+void strext_batch(dfmi_context* ctx, dfmi_agg_state* st, const dfmi::gb::Col* arg_cols, const unsigned* rg, int64_t m,
+                  uint64_t ngroups);
+void strext_batch_ungrouped(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* in,
+                            uint32_t flags);
+void strext_reset(dfmi_context* ctx, dfmi_agg_state* st);  // the device side emptied (the last finish's values stay)
+// the first ng groups' winners and the arena on the host (f.sx_ent, f.sx_arena)
+void strext_read(dfmi_context* ctx, dfmi_agg_state* st, FlatGroups& f, uint64_t ng);
+void strext_finish_ungrouped(dfmi_context* ctx, dfmi_agg_state* st, dfmi_agg_value* out);
+// group g's value of extreme x (StrExt::x index) in a finish's flat groups
+dfmi::aggh::StrVal strext_flat_value(const FlatGroups& f, size_t x, uint64_t g);
 
 }  // namespace agg
 }  // namespace dfmi

@@ -84,7 +84,7 @@ void build_agg_plan(const dfmi_agg_state* st, const dfmi_program* pred, const df
         for (const IrNode& nd : a->arg.ir)
             if (nd.rt_code) se.offer((uint64_t)(base + nd.ordinal) << 44, nd.rt_code, nd.rt_msg);
         jit::AggSpec s;
-        s.fn = acc_fn(a->fn);  // (an AVG accumulates as a SUM: the same kernel source and cache key)
+        s.fn = acc_fn(*a);  // (an AVG accumulates as a SUM, a Utf8 MIN / MAX as a COUNT: the same kernel source and cache key)
         s.prog = &a->arg;
         s.ord_base = base;
         s.arg_type = a->arg.type;
@@ -186,7 +186,7 @@ void dfmi::agg::flush_groups(dfmi_context* ctx, dfmi_agg_state* st) {
     const size_t n = st->aggs.size(), na = n + 1;
     const int kt = st->key.type;
     for (int g = 0; g <= st->win_width; ++g) {
-        std::vector<Partial> parts(na);
+        GroupState parts(na);
         for (size_t j = 0; j < na; ++j) {
             const bool is_min = j < n && st->aggs[j]->fn == DFMI_AGG_MIN;
             for (int c = 0; c < kAggCopies; ++c)
@@ -279,6 +279,7 @@ extern "C" int32_t dfmi_agg_state_create(dfmi_context* ctx, const dfmi_aggregate
         }
         HIP_TRY(hipSetDevice(ctx->device));
         alloc_accumulators(ctx, st.get(), kAggCopies, (size_t)n);
+        strext_create(ctx, st.get());
         *out = st.release();
         return DFMI_OK;
     });
@@ -311,7 +312,10 @@ extern "C" int32_t dfmi_agg_state_create_grouped_multi(dfmi_context* ctx, const 
         HIP_TRY(hipSetDevice(ctx->device));
         // one Boolean / integer key: the window kernel (16 consecutive values
         // per batch, more through the hash table); anything else: the hash table
-        if (num_keys == 1 && (kt == DFMI_TYPE_BOOLEAN || !host_keyed(kt))) {
+        // (a state with a Utf8 MIN / MAX takes no key window: every batch through the hash table, whose
+        // passes know each row's dense group id)
+        const bool strings = any_utf8_extreme(st->aggs.data(), st->aggs.size());
+        if (num_keys == 1 && (kt == DFMI_TYPE_BOOLEAN || !host_keyed(kt)) && !strings) {
             st->gslots = kt == DFMI_TYPE_BOOLEAN ? 3 : 17;  // false, true / 16 consecutive values; + null
             alloc_accumulators(ctx, st.get(), (size_t)kAggCopies * st->gslots, (size_t)n + 1);  // (+ the group's rows)
             if (kt != DFMI_TYPE_BOOLEAN) {
@@ -324,6 +328,7 @@ extern "C" int32_t dfmi_agg_state_create_grouped_multi(dfmi_context* ctx, const 
                 if (dfmi_agg_state_create(ctx, mm, 2, &st->mm_state, &e2) != DFMI_OK) throw Fail{e2.code, e2.message};
             }
         }
+        strext_create(ctx, st.get());
         *out = st.release();
         return DFMI_OK;
     });
@@ -366,6 +371,7 @@ extern "C" int32_t dfmi_agg_state_finish_grouped(dfmi_context* ctx, dfmi_agg_sta
         if (finish_flat(ctx, st, diag)) {
             const auto t0 = std::chrono::steady_clock::now();
             emit_flat(st, *st->flat, cap, keys, values, num_groups);
+            if (st->sx) st->sx->finished = true;  // (the values exist: dfmi_agg_state_value_bytes may be asked)
             if (diag.finish_profile)
                 fprintf(stderr, "[dfmi finish] emit %.1f us\n",
                         std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
@@ -373,6 +379,7 @@ extern "C" int32_t dfmi_agg_state_finish_grouped(dfmi_context* ctx, dfmi_agg_sta
         }
         collect_groups(ctx, st);
         emit_groups(st->groups, key_types(st), st->aggs.data(), st->aggs.size(), cap, keys, values, num_groups);
+        if (st->sx) st->sx->finished = true;
         return DFMI_OK;
     });
 }
@@ -394,6 +401,39 @@ extern "C" int32_t dfmi_agg_state_group_keys_utf8_part(const dfmi_agg_state* st,
     });
 }
 
+// The values of Utf8 MIN / MAX aggregate `agg` from the state's last finish, in its order.
+extern "C" int32_t dfmi_agg_state_value_bytes(const dfmi_agg_state* st, int32_t agg, int32_t* offsets,
+                                              int64_t num_offsets, uint8_t* data, int64_t data_capacity,
+                                              int64_t* data_length, dfmi_error* err) {
+    return guarded(err, [&]() -> int32_t {
+        if (!st || !data_length) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
+        *data_length = 0;
+        check_not_failed(st);
+        if (agg < 0 || agg >= (int32_t)st->aggs.size() || !is_utf8_extreme(*st->aggs[agg]) || !st->sx)
+            throw Fail{DFMI_ERR_INVALID_ARGUMENT, "not a Utf8 MIN / MAX aggregate of this state"};
+        if (!st->sx->finished) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "no finish yet"};
+        if (!st->grouped) {
+            emit_value_bytes(std::vector<StrVal>{st->sx->one[(size_t)agg]}, offsets, num_offsets, data, data_capacity, data_length);
+        } else if (!st->shown && st->flat) {
+            const FlatGroups& f = *st->flat;
+            size_t x = 0;
+            while (st->sx->x[x].agg != agg) ++x;
+            std::vector<StrVal> vals((size_t)f.ng);  // (a group without a counted row has no persisted winner: null)
+            for (uint64_t i = 0; i < f.ng; ++i) vals[i] = strext_flat_value(f, x, f.order[i]);
+            emit_value_bytes(vals, offsets, num_offsets, data, data_capacity, data_length);
+        } else {
+            emit_value_bytes(st->groups, agg, offsets, num_offsets, data, data_capacity, data_length);
+        }
+        return DFMI_OK;
+    });
+}
+
+// Internal test hook (not part of the C ABI, not declared in include/): the bytes reserved for the string
+// arena of a state's Utf8 MIN / MAX aggregates (0: none).
+extern "C" long long dfmi_internal_agg_str_arena_bytes(const dfmi_agg_state* st) {
+    return st && st->sx ? (long long)st->sx->arena_cap : 0;
+}
+
 extern "C" int32_t dfmi_agg_state_group_keys_utf8(const dfmi_agg_state* st, int32_t* offsets, int64_t num_offsets,
                                                   uint8_t* data, int64_t data_capacity, int64_t* data_length,
                                                   dfmi_error* err) {
@@ -407,6 +447,11 @@ extern "C" int32_t dfmi_agg_state_reset(dfmi_context* ctx, dfmi_agg_state* st, d
         if (st->acc.p)
             HIP_TRY(hipMemcpyAsync(st->acc.p, st->init.data(), st->acc_words * 8, hipMemcpyHostToDevice, ctx->stream));
         if (st->hd) reset_table(ctx, *st->hd);
+        strext_reset(ctx, st);
+        if (st->sx) {  // (and no finish to ask dfmi_agg_state_value_bytes about)
+            st->sx->finished = false;
+            st->sx->one.assign(st->aggs.size(), StrVal{});
+        }
         st->failed = false;
         st->failure = dfmi_error{};
         st->index.clear();
@@ -565,6 +610,17 @@ extern "C" int32_t dfmi_aggregate_batch(dfmi_context* ctx, dfmi_agg_state* st, c
             set_err(&st->failure, fail.code, fail.msg);
             throw fail;
         }
+        // Utf8 MIN / MAX (ungrouped; in the kernel above they counted): the string passes
+        // (the records have counted the batch: a failure here fails the query like the kernel's own)
+        if (!st->grouped && st->sx && n > 0) {
+            try {
+                strext_batch_ungrouped(ctx, st, pred, in, flags);
+            } catch (const Fail& f) {
+                st->failed = true;
+                set_err(&st->failure, f.code, f.msg);
+                throw;
+            }
+        }
         return DFMI_OK;
     });
 }
@@ -577,6 +633,7 @@ extern "C" int32_t dfmi_agg_state_finish(dfmi_context* ctx, dfmi_agg_state* st, 
         if (st->grouped) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "a GROUP BY state: dfmi_agg_state_finish_grouped"};
         const std::vector<Partial> parts = merge_copies(st, read_acc(ctx, st));
         for (size_t j = 0; j < st->aggs.size(); ++j) out[j] = finish_one(*st->aggs[j], parts[j]);
+        strext_finish_ungrouped(ctx, st, out);
         return DFMI_OK;
     });
 }
@@ -590,6 +647,7 @@ extern "C" int32_t dfmi_agg_state_partial(dfmi_context* ctx, dfmi_agg_state* st,
         if (!ctx || !st || !host_out) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         check_not_failed(st);
         if (st->grouped) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "partial state of a GROUP BY aggregate"};
+        if (st->sx) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, kUtf8ExtremePartial};
         const std::vector<Partial> parts = merge_copies(st, read_acc(ctx, st));
         memcpy(host_out, parts.data(), parts.size() * sizeof(Partial));
         return DFMI_OK;
@@ -601,6 +659,7 @@ extern "C" int64_t dfmi_agg_state_grouped_partial_bytes(dfmi_context* ctx, dfmi_
         if (!ctx || !st) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         if (!st->grouped) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "not a GROUP BY state"};
         check_not_failed(st);
+        if (st->sx) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, kUtf8ExtremePartial};
         HIP_TRY(hipSetDevice(ctx->device));
         collect_groups(ctx, st);
         return (int64_t)grouped_bytes(st->groups, st->aggs.size());
@@ -613,6 +672,7 @@ extern "C" int32_t dfmi_agg_state_grouped_partial(dfmi_context* ctx, dfmi_agg_st
         if (!ctx || !st || !host_out) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
         if (!st->grouped) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "not a GROUP BY state"};
         check_not_failed(st);
+        if (st->sx) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, kUtf8ExtremePartial};
         HIP_TRY(hipSetDevice(ctx->device));
         collect_groups(ctx, st);
         if ((size_t)bytes < grouped_bytes(st->groups, st->aggs.size()))
@@ -631,6 +691,7 @@ int32_t dfmi_agg_state_show_merged(dfmi_agg_state* st, const void* const* partia
     return guarded(err, [&]() -> int32_t {
         if (!st || !st->grouped || !partials || !sizes || nparts <= 0 || !num_groups)
             throw Fail{DFMI_ERR_INVALID_ARGUMENT, "bad argument"};
+        if (st->sx) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, kUtf8ExtremePartial};
         auto merged = std::make_shared<GroupMap>();
         std::vector<int> kt = key_types(st);
         merge_serialized(*merged, kt, st->aggs.data(), st->aggs.size(), partials, sizes, nparts);

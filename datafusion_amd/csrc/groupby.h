@@ -114,6 +114,7 @@ struct AccArgs {
     unsigned long long* acc;       // [groups][words]
     Hdr* hdr;
     int32_t* coll_rows;            // [m] rows whose key differs from the slot's
+    unsigned* rg;                  // optional [m]: the row's group id, ~0u: not added here (listed); nullptr: not kept
 };
 
 // Bucketed accumulation (many rows per group: agg_hash.cpp use_buckets). The
@@ -257,6 +258,11 @@ struct ConcatJob {
 };
 hipError_t launch_concat(const unsigned long long* srcs, const ConcatJob* jobs, int njobs, const long long* prefix,
                          int nb, long long m, hipStream_t stream);
+
+// The m bits of a Boolean bitmap as m UInt8 values 0 / 1: the argument of a
+// Boolean MIN / MAX, which the passes above then take as a UInt8 column.
+// `dst` holds (m + 7) / 8 * 8 bytes, 8-byte aligned.
+hipError_t launch_bits_to_u8(const unsigned char* bits, unsigned char* dst, long long m, hipStream_t stream);
 
 // groupby.hip: launches on `stream` (asynchronous)
 hipError_t launch_claim(const ClaimArgs& a, hipStream_t stream);

@@ -463,6 +463,7 @@ __global__ __launch_bounds__(256) void k_group_accumulate(const AccArgs A) {
         const long long i = base + lane;
         unsigned g = 0;
         const bool ok = i < A.m && row_group<NK>(A.k, A.m, A.epoch, A.t, A.arena, A.arena_cap, A.hdr, A.coll_rows, A.sidx, i, g);
+        if (A.rg && i < A.m) A.rg[i] = ok ? g : ~0u;
         u64 active = __ballot(ok);
         int singles = 0;
         while (active) {
@@ -1239,6 +1240,17 @@ __global__ __launch_bounds__(256) void k_group_concat(const u64* srcs, const Con
     }
 }
 
+// A Boolean bitmap's m bits as a UInt8 column of 0 / 1 (the argument of a
+// Boolean MIN / MAX presented to the passes above as an integer column): one
+// source byte -> one 8-byte store; dst holds (m + 7) / 8 * 8 bytes.
+__global__ __launch_bounds__(256) void k_group_bits_to_u8(const u8* bits, u64* dst, long long nbytes) {
+    for (long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x; b < nbytes; b += (long long)gridDim.x * blockDim.x) {
+        const u64 x = bits[b];
+        // bit q of x to byte q: spread with a multiply, keep each byte's low bit
+        dst[b] = (((x & 0x7full) * 0x0002040810204081ull) & 0x0001010101010101ull) | ((x >> 7) << 56);
+    }
+}
+
 static int grid_for(long long items, int per_block = 256, int cap = 8192) {
     long long g = (items + per_block - 1) / per_block;
     return (int)(g < 1 ? 1 : (g > cap ? cap : g));
@@ -1273,6 +1285,13 @@ hipError_t launch_concat(const unsigned long long* srcs, const ConcatJob* jobs, 
     if (nb < 1 || nb > kConcatMaxBatches || njobs < 1) return hipErrorInvalidValue;
     if (m <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_group_concat, dim3(grid_for(m, 256, 2048), njobs), dim3(256), 0, st, srcs, jobs, prefix, nb, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_bits_to_u8(const unsigned char* bits, unsigned char* dst, long long m, hipStream_t st) {
+    if (m <= 0) return hipSuccess;
+    const long long nbytes = (m + 7) / 8;
+    hipLaunchKernelGGL(k_group_bits_to_u8, dim3(grid_for(nbytes, 256, 2048)), dim3(256), 0, st, bits, (u64*)dst, nbytes);
     return hipGetLastError();
 }
 

@@ -722,6 +722,12 @@ static std::vector<int> agg_arg_slots(const Plan& P, const Launch& X) {
     return out;
 }
 
+// The operand of a MIN / MAX as agg_key / agg_isnan take it: a Boolean
+// argument (DFMI_FLAG_EXT_AGG_MINMAX_ANY) is an integer extreme over 0 / 1.
+static std::string extreme_operand(const AggSpec& a, const std::string& v) {
+    return a.arg_type == DFMI_TYPE_BOOLEAN ? "(unsigned char)((" + v + ") ? 1 : 0)" : v;
+}
+
 // Fused Selection + Aggregate kernel (DFMI_FLAG_EXT_AGGREGATE): no compaction
 // and no look-back -- the selected rows' argument values are reduced in
 // registers, the block's partial goes to a global accumulator copy
@@ -773,10 +779,11 @@ static void generate_agg(Gen& g, std::ostringstream& o, const Plan& P, Launch& X
                   << "], (double)(" << v.v << "), fin_, lane);\n";
             } else if (a.fn == DFMI_AGG_MIN || a.fn == DFMI_AGG_MAX) {
                 const char* cmp = a.fn == DFMI_AGG_MIN ? "<" : ">";
-                o << "      const bool nan_ = dfmi::agg_isnan(" << v.v << ");\n"
+                const std::string xv = extreme_operand(a, v.v);
+                o << "      const bool nan_ = dfmi::agg_isnan(" << xv << ");\n"
                   << "      afl" << j << " |= " << ok
                   << " ? (nan_ ? (unsigned)dfmi::AGGF_NAN : (unsigned)dfmi::AGGF_VALUE) : 0u;\n"
-                  << "      if (" << ok << " && !nan_) { const u64 k_ = dfmi::agg_key(" << v.v << "); if (k_ " << cmp
+                  << "      if (" << ok << " && !nan_) { const u64 k_ = dfmi::agg_key(" << xv << "); if (k_ " << cmp
                   << " akey" << j << ") akey" << j << " = k_; }\n";
             }
             o << "    }\n";
@@ -962,9 +969,10 @@ static void generate_agg_grouped(Gen& g, std::ostringstream& o, const Plan& P, L
               << a.fslot << "], (double)(" << v.v << "), fin_, lane);\n";
         } else if (a.fn == DFMI_AGG_MIN || a.fn == DFMI_AGG_MAX) {
             const char* cmp = a.fn == DFMI_AGG_MIN ? "<" : ">";
-            o << "      const bool nan_ = dfmi::agg_isnan(" << v.v << ");\n"
+            const std::string xv = extreme_operand(a, v.v);
+            o << "      const bool nan_ = dfmi::agg_isnan(" << xv << ");\n"
               << "      afl" << j << " |= " << ok << " ? (nan_ ? (unsigned)dfmi::AGGF_NAN : (unsigned)dfmi::AGGF_VALUE) : 0u;\n"
-              << "      if (" << ok << " && !nan_) { const u64 k_ = dfmi::agg_key(" << v.v << "); if (k_ " << cmp << " akey" << j
+              << "      if (" << ok << " && !nan_) { const u64 k_ = dfmi::agg_key(" << xv << "); if (k_ " << cmp << " akey" << j
               << ") akey" << j << " = k_; }\n";
         }
         o << "    }\n";

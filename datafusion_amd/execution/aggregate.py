@@ -27,6 +27,8 @@ _NP = {
 def agg_value_array(v) -> Array:
     """A one-row Array holding an aggregate value (dfmi_agg_value)."""
     t = DataType(v.type)
+    if t == DataType.Boolean:  # MIN / MAX of a Boolean argument (DFMI_FLAG_EXT_AGG_MINMAX_ANY)
+        return Array.from_numpy(t, np.array([bool(v.bits)]), np.array([False]) if v.is_null else None)
     dt = np.dtype(_NP[t])
     raw = np.array([v.bits], dtype=np.uint64).view(np.uint8)[: dt.itemsize].copy()
     vals = raw.view(dt)
@@ -150,8 +152,9 @@ class AggregateRelation(Relation):
                 if b is None:
                     break
                 state.add(self.predicate, b, self.flags)
-        if self.keys is None:
-            return RecordBatch(self._schema, [agg_value_array(v) for v in state.finish()])
+        if self.keys is None:  # (a Utf8 MIN / MAX: its bytes from the state, None for null)
+            return RecordBatch(self._schema, [Array.from_strings(state.value_strings(j)) if DataType(v.type) == DataType.Utf8
+                                              else agg_value_array(v) for j, v in enumerate(state.finish())])
         keys, vals = state.finish()
         if len(keys) == 0:
             return None
@@ -163,7 +166,11 @@ class AggregateRelation(Relation):
                 cols.append(Array.from_strings(state.key_strings(p)))
             else:
                 cols.append(agg_values_array(kv))
-        cols += [agg_values_array(vals[:, j]) for j in range(len(self.aggs))]
+        for j in range(len(self.aggs)):
+            if DataType(int(vals[0, j]["type"])) == DataType.Utf8:
+                cols.append(Array.from_strings(state.value_strings(j)))
+            else:
+                cols.append(agg_values_array(vals[:, j]))
         return RecordBatch(self._schema, cols)
 
     def schema(self) -> Schema:

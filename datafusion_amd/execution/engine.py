@@ -575,7 +575,27 @@ class AggState:
         rc = _abi.lib().dfmi_agg_state_finish(self.eng.ctx, self.handle, out, C.byref(err))
         if rc != _abi.DFMI_OK:
             raise ExecutionError.from_status(rc, err.message.decode("utf-8", errors="replace"))
-        return list(out)
+        self._last_values = list(out)
+        return self._last_values
+
+    def _value_bytes(self, j: int, rows: int, nulls) -> List[Optional[bytes]]:
+        self.eng.drain()
+        L = _abi.lib()
+        err = _abi.dfmi_error()
+        ln = C.c_int64()
+        L.dfmi_agg_state_value_bytes(self.handle, j, None, 0, None, 0, C.byref(ln), C.byref(err))  # (the length)
+        offs = np.zeros(rows + 1, np.int32)
+        data = np.zeros(max(1, ln.value), np.uint8)
+        rc = L.dfmi_agg_state_value_bytes(self.handle, j, offs.ctypes.data, offs.size, data.ctypes.data, data.size,
+                                          C.byref(ln), C.byref(err))
+        if rc != _abi.DFMI_OK:
+            raise ExecutionError.from_status(rc, err.message.decode("utf-8", errors="replace"))
+        return [None if nulls[g] else bytes(data[offs[g]:offs[g + 1]]) for g in range(rows)]
+
+    def value_strings(self, j: int) -> List[Optional[bytes]]:
+        """The value of Utf8 MIN / MAX aggregate j of the last finish() (one
+        row; None for null): dfmi_agg_state_value_bytes."""
+        return self._value_bytes(j, 1, [self._last_values[j].is_null])
 
     def partial(self) -> bytes:
         """The exact partial state (for merging shards: dfmi_agg_merge_partials)."""
@@ -633,6 +653,12 @@ class GroupedAggState(AggState):
             raise ExecutionError.from_status(rc, err.message.decode("utf-8", errors="replace"))
         nulls = [(k[part] if self.multi else k).is_null for k in keys]
         return [None if nulls[g] else bytes(data[offs[g]:offs[g + 1]]) for g in range(len(keys))]
+
+    def value_strings(self, j: int) -> List[Optional[bytes]]:
+        """The values of Utf8 MIN / MAX aggregate j of the groups of the last
+        finish(), in its order (None for null): dfmi_agg_state_value_bytes."""
+        _, vals = self._last
+        return self._value_bytes(j, len(vals), [bool(v[j].is_null) for v in vals])
 
     def partial(self) -> bytes:
         """The exact per-group partial state (dfmi_agg_state_grouped_partial)."""

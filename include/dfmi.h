@@ -271,6 +271,44 @@ typedef struct dfmi_expr_node {
  * both flags every expression compiles and fails exactly as before. One flag
  * bit, no struct change, no new entry point: DFMI_ABI_VERSION stays 4. */
 
+#define DFMI_FLAG_EXT_AGG_MINMAX_ANY 0x200u
+/* With DFMI_FLAG_EXT_AGGREGATE (alone it changes nothing): `min` / `max`
+ * (any letter case) over a Boolean or Utf8 argument instead of
+ * DFMI_ERR_NOT_IMPLEMENTED "aggregate over Boolean" / "aggregate over Utf8";
+ * return_type = the argument's type. The planner builds the plan
+ * (sqlplanner.rs:296-303) and the reference's aggregate fixtures expect it;
+ * nothing in the reference runs it, so the feature is build-defined, parity
+ * pinned only by those fixture cells.
+ *   rows:     a row counts exactly when COUNT(e) counts it on the same path:
+ *             valid slots only, and after a Selection (no validity,
+ *             filter.rs:84-93) a selected null slot counts with its raw bit /
+ *             slot bytes; dfmi_agg_value.count is that count, and the result
+ *             is null when no row counts;
+ *   Boolean:  false < true; type Boolean, bits 0 / 1. Its partial is an
+ *             integer MIN / MAX partial over 0 / 1 -- the wire format is
+ *             unchanged and every merge / shard entry point takes it -- and it
+ *             runs everywhere numeric MIN / MAX runs (ungrouped, key window,
+ *             hash table, every batch form, host merge, device finish);
+ *   Utf8:     the GROUP BY / ORDER BY / DFMI_FLAG_EXT_UTF8_ORDER order:
+ *             sequences of unsigned bytes, the first differing byte decides, a
+ *             proper prefix is less; 0x00 and 0x80-0xFF are ordinary bytes;
+ *             the empty string is the least value and not null. type Utf8,
+ *             bits = the value's byte length (0 for null); the bytes come from
+ *             dfmi_agg_state_value_bytes. The result does not depend on row
+ *             order, batch size or path. The argument must be something the
+ *             evaluation pass produces for COUNT(e) (in practice a column).
+ *             Ungrouped states and grouped states of 1 to 4 keys of any type,
+ *             every batch form, further batches after a finish, reset;
+ *   partials: of a state or a merge with a Utf8 MIN / MAX: the wire format
+ *             carries no string -- dfmi_agg_state_partial,
+ *             dfmi_agg_state_grouped_partial(_bytes), dfmi_shard_agg_finish*,
+ *             dfmi_agg_merge_partials and dfmi_agg_merge_grouped_partials*
+ *             return DFMI_ERR_NOT_IMPLEMENTED "partial state of a Utf8 MIN /
+ *             MAX aggregate".
+ * `sum` / `avg` over Boolean / Utf8 keep their errors. Without both flags
+ * every call compiles, runs and fails as before. One flag bit and one entry
+ * point, no struct change: DFMI_ABI_VERSION stays 4. */
+
 /* Signature of a built-in scalar function, for a binding's
  * SchemaProvider::get_function_meta (sqlplanner.rs:330-350 casts each
  * argument to arg_types[i]). Returns 0 and fills *num_args, *return_type and
@@ -666,6 +704,15 @@ int32_t dfmi_agg_state_group_keys_utf8_part(const dfmi_agg_state* state, int32_t
                                             int64_t* data_length, dfmi_error* err);
 int32_t dfmi_agg_state_group_keys_utf8(const dfmi_agg_state* state, int32_t* offsets, int64_t num_offsets, uint8_t* data,
                                        int64_t data_capacity, int64_t* data_length, dfmi_error* err);
+/* DFMI_FLAG_EXT_AGG_MINMAX_ANY: the values of aggregate `agg` (a MIN / MAX
+ * over a Utf8 argument) from the state's last dfmi_agg_state_finish (one row)
+ * or dfmi_agg_state_finish_grouped (num_groups rows, the same order), as an
+ * arrow BinaryArray: offsets from 0, a null value's slot empty (the finish's
+ * is_null says which). *data_length is always set; a capacity that is too
+ * small gives DFMI_ERR_CAPACITY and nothing is written. `agg` out of range or
+ * not a Utf8 MIN / MAX, or no finish yet: DFMI_ERR_INVALID_ARGUMENT. */
+int32_t dfmi_agg_state_value_bytes(const dfmi_agg_state* state, int32_t agg, int32_t* offsets, int64_t num_offsets,
+                                   uint8_t* data, int64_t data_capacity, int64_t* data_length, dfmi_error* err);
 /* Multi-GPU GROUP BY: the exact per-group partial state (every key part --
  * Utf8 bytes included --, the group's selected rows, every aggregate's
  * partial) as host bytes -- size first (negative: -status) -- and the merge
