@@ -52,8 +52,9 @@ struct Failure {
 };
 
 Fail device_fail(int kind) {
-    return kind == ERRK_DIV_ZERO ? Fail{DFMI_ERR_DIVIDE_BY_ZERO, "DivideByZero"}
-                                 : Fail{DFMI_ERR_PANIC, "attempt to divide with overflow"};
+    if (kind == ERRK_DIV_ZERO) return Fail{DFMI_ERR_DIVIDE_BY_ZERO, "DivideByZero"};
+    return Fail{DFMI_ERR_PANIC, kind == ERRK_REM_OVERFLOW ? "attempt to calculate the remainder with overflow"
+                                                          : "attempt to divide with overflow"};
 }
 
 // Batches [0, nb) through ONE launch of st's batched kernel (ungrouped, or

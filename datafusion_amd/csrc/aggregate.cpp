@@ -600,8 +600,11 @@ extern "C" int32_t dfmi_aggregate_batch(dfmi_context* ctx, dfmi_agg_state* st, c
         if (dev_kind == ERRK_CAPACITY)  // a key outside the window the pre-pass found: cannot happen
             fail = Fail{DFMI_ERR_DEVICE, "GROUP BY key outside the batch's key window"};
         else if (dev_kind && (!se.set || dev_key < se.key))
-            fail = dev_kind == ERRK_DIV_ZERO ? Fail{DFMI_ERR_DIVIDE_BY_ZERO, "DivideByZero"}
-                                             : Fail{DFMI_ERR_PANIC, "attempt to divide with overflow"};
+            fail = dev_kind == ERRK_DIV_ZERO
+                       ? Fail{DFMI_ERR_DIVIDE_BY_ZERO, "DivideByZero"}
+                       : Fail{DFMI_ERR_PANIC, dev_kind == ERRK_REM_OVERFLOW
+                                                  ? "attempt to calculate the remainder with overflow"
+                                                  : "attempt to divide with overflow"};
         else if (se.set)
             fail = Fail{se.code, se.msg};
         if (fail.code != DFMI_OK) {

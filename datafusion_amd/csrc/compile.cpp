@@ -323,7 +323,9 @@ int compile_node(const Builder& b, int t, const dfmi_schema& s, uint32_t flags, 
                     ir.rt_code = DFMI_ERR_PANIC;
                     ir.rt_msg = "called `Option::unwrap()` on a `None` value";
                 }
-            } else if (n.op >= DFMI_OP_PLUS && n.op <= DFMI_OP_DIVIDE) {
+            } else if ((n.op >= DFMI_OP_PLUS && n.op <= DFMI_OP_DIVIDE) ||
+                       (n.op == DFMI_OP_MODULUS && (flags & DFMI_FLAG_EXT_MODULUS))) {
+                // (Modulus: extension, math_ops! as the other four)
                 ir.type = lt;  // op_type = left_expr.get_type()
                 if (!(lt == rt && is_numeric_type(lt))) {
                     ir.rt_code = DFMI_ERR_EXECUTION;

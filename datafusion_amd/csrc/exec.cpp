@@ -690,6 +690,8 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
         if (dev_kind && (!se.set || dev_key < se.key)) {
             ctx->last_err_key = dev_key;
             if (dev_kind == ERRK_DIV_ZERO) throw Fail{DFMI_ERR_DIVIDE_BY_ZERO, "DivideByZero"};
+            if (dev_kind == ERRK_REM_OVERFLOW)
+                throw Fail{DFMI_ERR_PANIC, "attempt to calculate the remainder with overflow"};
             throw Fail{DFMI_ERR_PANIC, "attempt to divide with overflow"};
         }
         if (se.set) {
@@ -1020,6 +1022,8 @@ int32_t dfmi::filter_project_batches_staged(dfmi_context* ctx, const dfmi_progra
                 if (kind == ERRK_CAPACITY) throw Fail{DFMI_ERR_CAPACITY, "Utf8 output data_capacity too small"};
                 ctx->last_err_key = key & ~15ull;
                 if (kind == ERRK_DIV_ZERO) throw Fail{DFMI_ERR_DIVIDE_BY_ZERO, "DivideByZero"};
+                if (kind == ERRK_REM_OVERFLOW)
+                    throw Fail{DFMI_ERR_PANIC, "attempt to calculate the remainder with overflow"};
                 throw Fail{DFMI_ERR_PANIC, "attempt to divide with overflow"};
             }
             const int64_t n = ins[b].num_rows;

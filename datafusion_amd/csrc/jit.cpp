@@ -35,6 +35,7 @@
 
 #include "dfmi_program.h"
 #include "jit.h"
+#include "rem_literal.h"
 
 extern const char dfmi_skeleton_src[];  // jit_skeleton.hip, embedded by the Makefile
 namespace {
@@ -57,6 +58,13 @@ const char* math_sym(int op) {
     static const char* s[] = {"+", "-", "*", "/"};
     return s[op - DFMI_OP_PLUS];
 }
+
+// Modulus by an integer literal: the reciprocal path (irem_lit) unless
+// DFMI_DIAG=1 DFMI_REM_LITERAL=0 forces the general one (A/B runs; read once).
+const bool g_rem_literal = [] {
+    const char* e = getenv("DFMI_DIAG") ? getenv("DFMI_REM_LITERAL") : nullptr;
+    return !e || atoi(e) != 0;
+}();
 
 bool is_float(int t) { return t == DFMI_TYPE_FLOAT32 || t == DFMI_TYPE_FLOAT64; }
 bool is_signed_int(int t) { return t >= DFMI_TYPE_INT8 && t <= DFMI_TYPE_INT64; }
@@ -356,6 +364,22 @@ struct Gen {
                   << a.v << ", " << b.v << ");\n";
             else
                 o << "    " << ct << " " << v << " = dfmi::idiv<" << ct << ">(" << a.v << ", " << b.v << ");\n";
+        } else if (op == DFMI_OP_MODULUS) {  // extension: the Divide arm's shape -- the checks, then the value
+            o << "    if ((" << act << ") && " << valid << ") {\n"
+              << "      if ((" << b.v << ") == (" << ct << ")0) dfmi::report_err(A.err, " << ord
+              << ", row, dfmi::ERRK_DIV_ZERO);\n";
+            if (is_signed_int(ty))
+                o << "      else if ((" << b.v << ") == (" << ct << ")-1 && (" << a.v << ") == dfmi::int_min<" << ct
+                  << ">()) dfmi::report_err(A.err, " << ord << ", row, dfmi::ERRK_REM_OVERFLOW);\n";
+            o << "    }\n";
+            const IrNode& R = p->ir[n.r];
+            if (f)  // (a literal divisor too)
+                o << "    " << ct << " " << v << " = dfmi::fn_mod<" << ct << ">(" << a.v << ", " << b.v << ");\n";
+            else if (R.kind == IR_LIT && g_rem_literal)  // the reciprocal in a literal slot of its own
+                o << "    " << ct << " " << v << " = dfmi::irem_lit<" << ct << ">(" << a.v << ", " << b.v << ", A.lits["
+                  << lit(rem_reciprocal(type_width(ty), is_signed_int(ty), R.bits)) << "]);\n";
+            else
+                o << "    " << ct << " " << v << " = dfmi::irem<" << ct << ">(" << a.v << ", " << b.v << ");\n";
         } else if (f) {
             o << "    " << ct << " " << v << " = dfmi::sse_nan<" << ct << ">((" << a.v << ") " << math_sym(op) << " ("
               << b.v << "), " << a.v << ", " << b.v << ");\n";

@@ -100,7 +100,13 @@ __device__ __forceinline__ void clear_previous(const Args& A, unsigned block, in
     if ((A.mode & 16) && block == 0 && tid == 0) atomicMax(A.err, ~(u64)3);
 }
 
-enum ErrKind : unsigned { ERRK_DIV_ZERO = 1, ERRK_DIV_OVERFLOW = 2, ERRK_LOOKBACK_TIMEOUT = 3, ERRK_CAPACITY = 4 };
+enum ErrKind : unsigned {
+    ERRK_DIV_ZERO = 1,
+    ERRK_DIV_OVERFLOW = 2,
+    ERRK_LOOKBACK_TIMEOUT = 3,
+    ERRK_CAPACITY = 4,
+    ERRK_REM_OVERFLOW = 5  // Modulus: iN::MIN % -1 (the kind field of report_err's key has 4 bits)
+};
 
 constexpr u64 FLAG_A = 1ull << 62;
 constexpr u64 FLAG_P = 2ull << 62;
@@ -217,6 +223,107 @@ __device__ __noinline__ T idiv(T x, T y) {
     }
     return (T)(x / y);
 }
+
+// ---- modulus helpers: begin ------------------------------------------------
+// Modulus extension (DFMI_FLAG_EXT_MODULUS): Rust `%` on iN / uN -- the
+// truncated remainder, the sign of the dividend, computed in the operand's
+// width. A zero divisor is DivideByZero and iN::MIN % -1 panics; both are
+// reported by the caller, the value here only has to be defined (0). Plain
+// C++ between the two markers, no Args and no wave intrinsics:
+// tests/native/modulus_driver.cpp compiles this very text for the host (it
+// defines DFMI_REM_FN, DFMI_REM_OUTLINE and the integer typedefs) and checks
+// it against C++ `%` under the sanitizers.
+#ifndef DFMI_REM_FN
+#define DFMI_REM_FN __device__ __forceinline__
+#define DFMI_REM_OUTLINE __device__ __noinline__
+#endif
+
+// The unsigned type a remainder of T is worked in: 32 bits for operands of up
+// to 32 bits, 64 bits for 64-bit operands.
+template <int BYTES>
+struct RemWord {
+    typedef u32 U;
+    typedef i32 S;
+};
+template <>
+struct RemWord<8> {
+    typedef u64 U;
+    typedef i64 S;
+};
+
+// The general path's remainder in the working width W (i32 / u32 / i64 / u64),
+// defined for every input. Out of line: gfx950 has no integer divide, the
+// 64-bit sequence is ~140 instructions.
+template <typename W>
+DFMI_REM_OUTLINE W irem_word(W x, W y) {
+    if (y == (W)0) return (W)0;
+    if constexpr ((W)-1 < (W)0) {
+        if (y == (W)-1) return (W)0;  // (MIN % -1 would trap on the host and is undefined in C++)
+    }
+    return (W)(x % y);
+}
+
+// x % y for a divisor that varies by row. Int8 / Int16 / UInt8 / UInt16 are
+// widened to 32 bits (the remainder of the widened values is the narrow one).
+template <typename T>
+DFMI_REM_FN T irem(T x, T y) {
+    if constexpr ((T)-1 < (T)0) {
+        typedef typename RemWord<sizeof(T)>::S W;
+        return (T)irem_word<W>((W)x, (W)y);
+    } else {
+        typedef typename RemWord<sizeof(T)>::U W;
+        return (T)irem_word<W>((W)x, (W)y);
+    }
+}
+
+// High N bits of the 2N-bit product.
+DFMI_REM_FN u32 rem_mulhi(u32 a, u32 b) { return (u32)(((u64)a * (u64)b) >> 32); }
+DFMI_REM_FN u64 rem_mulhi(u64 a, u64 b) {
+    const u64 a0 = (u32)a, a1 = a >> 32, b0 = (u32)b, b1 = b >> 32;
+    const u64 p00 = a0 * b0, p01 = a0 * b1, p10 = a1 * b0, p11 = a1 * b1;
+    const u64 mid = (p00 >> 32) + (u32)p01 + (u32)p10;  // < 3 * 2^32
+    return p11 + (p01 >> 32) + (p10 >> 32) + (mid >> 32);
+}
+
+// x % d for a literal (wave-uniform) divisor d, with the host's
+// m = floor((2^N - 1) / |d|), N = 32 or 64 the working width (m = 0 for d = 0):
+// q^ = mulhi_N(|x|, m) is floor(|x| / |d|) or one less for every |d| >= 1
+// (m = 2^N / |d| - e with 0 < e <= 1, so |x| * m / 2^N = |x| / |d| - |x| * e / 2^N,
+// the last term in [0, 1)), so r = |x| - q^ * |d| needs at most one
+// subtraction of |d|; the sign of x is reapplied. |MIN| fits the unsigned
+// type. A 64-bit operand takes the 32-bit form per lane where it can (below). The same bits as irem<T>(x, d) for every x and d (d = 0: 0;
+// MIN % -1: 0).
+template <typename T>
+DFMI_REM_FN T irem_lit(T x, T d, u64 m) {
+    typedef typename RemWord<sizeof(T)>::U U;
+    constexpr bool sgn = (T)-1 < (T)0;
+    U ax = (U)x, ad = (U)d;  // a signed narrow value sign-extends to the working width
+    bool neg = false;
+    if constexpr (sgn) {
+        neg = x < (T)0;
+        if (neg) ax = (U)0 - ax;
+        if (d < (T)0) ad = (U)0 - ad;
+    }
+    if (ad == (U)0) return (T)0;
+    U r;
+    bool small = false;
+    if constexpr (sizeof(U) == 8) small = ((ax | ad) >> 32) == 0;
+    if (small) {
+        // a 64-bit operand whose |x| and |d| both fit 32 bits (a column cast
+        // up from a narrower type, small keys): the 32-bit reduction, a fifth
+        // of the instructions. Its reciprocal floor((2^32 - 1) / |d|) is
+        // m >> 32: no multiple of |d| lies in (2^32 - 1, 2^32 - 2^-32].
+        const u32 a32 = (u32)ax, d32 = (u32)ad;
+        u32 r32 = a32 - rem_mulhi(a32, (u32)(m >> 32)) * d32;
+        if (r32 >= d32) r32 -= d32;
+        r = (U)r32;
+    } else {
+        r = ax - rem_mulhi(ax, (U)m) * ad;
+        if (r >= ad) r -= ad;
+    }
+    return (T)(neg ? (U)0 - r : r);
+}
+// ---- modulus helpers: end --------------------------------------------------
 
 // NaN results of a Float32 / Float64 operator as the reference's scalar
 // loops produce them on x86-64 (SSE2, left operand first): a NaN operand

@@ -1,7 +1,7 @@
 // Build-time check of jit_skeleton.hip: instantiates every skeleton template
 // with a representative generated body (one Float64 predicate, a gathered
-// column, a Utf8 gather, integer division at several widths, every scalar
-// function helper), so a broken skeleton fails `make` rather than the
+// column, a Utf8 gather, integer division at several widths, the remainder
+// helpers at every width, every scalar function helper), so a broken skeleton fails `make` rather than the
 // first query compile on the GPU. Not linked into libdfmi.so.
 #include <hip/hip_runtime.h>
 
@@ -73,6 +73,18 @@ extern "C" __global__ __launch_bounds__(512) void dfmi_skeleton_check(const dfmi
     if (tid == 0 && dfmi::bitmap_word(A.valid[0], 0, A.n_rows) == 7)
         A.totals[0] = (u64)dfmi::idiv<i64>((i64)A.lits[1], (i64)A.lits[2]) +
                       (u64)dfmi::idiv<i8>((i8)A.lits[1], dfmi::int_min<i8>()) + dfmi::idiv<u16>((u16)A.lits[1], 3);
+    // Modulus extension: the general and the literal-divisor remainder at every width
+    if (tid == 1 && dfmi::bitmap_word(A.valid[0], 0, A.n_rows) == 7) {
+        const u64 x = A.lits[1], y = A.lits[2], m = A.lits[4];
+        A.totals[1] = (u64)dfmi::irem<i64>((i64)x, (i64)y) + dfmi::irem<u64>(x, y) + (u64)dfmi::irem<i32>((i32)x, (i32)y) +
+                      dfmi::irem<u32>((u32)x, (u32)y) + (u64)dfmi::irem<i16>((i16)x, (i16)y) +
+                      dfmi::irem<u16>((u16)x, (u16)y) + (u64)dfmi::irem<i8>((i8)x, (i8)y) + dfmi::irem<u8>((u8)x, (u8)y);
+        A.totals[2] = (u64)dfmi::irem_lit<i64>((i64)x, (i64)y, m) + dfmi::irem_lit<u64>(x, y, m) +
+                      (u64)dfmi::irem_lit<i32>((i32)x, (i32)y, m) + dfmi::irem_lit<u32>((u32)x, (u32)y, m) +
+                      (u64)dfmi::irem_lit<i16>((i16)x, (i16)y, m) + dfmi::irem_lit<u16>((u16)x, (u16)y, m) +
+                      (u64)dfmi::irem_lit<i8>((i8)x, (i8)y, m) + dfmi::irem_lit<u8>((u8)x, (u8)y, m);
+        dfmi::report_err(A.err, 2, base, dfmi::ERRK_REM_OVERFLOW);
+    }
     // scalar function extension: every helper, Float64 and Float32
     {
         const double x = dfmi::f64(c0[0]), y = dfmi::f64(A.lits[3]);

@@ -309,6 +309,49 @@ typedef struct dfmi_expr_node {
  * every call compiles, runs and fails as before. One flag bit and one entry
  * point, no struct change: DFMI_ABI_VERSION stays 4. */
 
+#define DFMI_FLAG_EXT_MODULUS      0x400u
+/* Operator::Modulus (DFMI_OP_MODULUS, SQL `%`; planned by sqlplanner.rs:263,
+ * executed nowhere in the reference) instead of the compile error
+ * ExecutionError("operator: Modulus"). Without the flag -- whatever other
+ * flags are set -- that error stays exactly as it is, and the generated code
+ * of an expression without a Modulus node does not change with the flag.
+ * Beyond the reference's two fixtures (numerics_modulo*.csv) the feature is
+ * build-defined, parity unpinned.
+ *   types:    as Plus / Minus / Multiply / Divide (math_ops!): the result has
+ *             the left operand's type; both operands must have the same type,
+ *             one of Int8..Int64, UInt8..UInt64, Float32, Float64. Anything
+ *             else (Int64 % Float64, Utf8, Boolean) compiles and carries the
+ *             run-time ExecutionError("math_ops") at the node's ordinal, as
+ *             for the other four. The name is "<l> Modulus <r>";
+ *   nulls:    null (value slot zero) where either side is null; a null row
+ *             raises nothing;
+ *   integers: Rust's `%`: the truncated remainder with the sign of the
+ *             dividend (-7 % 3 = -1, 7 % -3 = 1), computed in the operand's
+ *             width. For non-null operands of a selected row, and only
+ *             those: a zero divisor is DFMI_ERR_DIVIDE_BY_ZERO
+ *             "DivideByZero" (the rule of Divide), and iN::MIN % -1 is Rust's
+ *             panic, DFMI_ERR_PANIC "attempt to calculate the remainder with
+ *             overflow";
+ *   floats:   Rust's f64 % / f32 % on x86-64 (C fmod: exact, the sign of the
+ *             dividend, |result| < |divisor|), in the operand's width. A
+ *             non-null +-0.0 divisor is DFMI_ERR_DIVIDE_BY_ZERO, checked
+ *             before any NaN rule, as for Divide. Otherwise a NaN operand
+ *             comes back quieted (the left one first) and an infinite
+ *             dividend gives the default NaN. THE DIFFERENCE to the scalar
+ *             function mod(x, y) (DFMI_FLAG_EXT_SCALAR_FUNCTIONS) is the zero
+ *             divisor alone: mod() returns the default NaN and raises nothing,
+ *             the operator raises DivideByZero; every other value is the same;
+ *   errors:   the operands' ordinals come before the node's own, and the
+ *             first error by (ordinal, row) is the one reported, so sharded,
+ *             chunked and coalesced runs report what one pass would;
+ *   where:    wherever Divide runs -- predicates, projections, aggregate
+ *             arguments, GROUP BY / ORDER BY key expressions; every batch form.
+ * A literal divisor (`col % 10`) is reduced by a reciprocal the host computes
+ * per launch and passes in a literal slot of its own (32 slots per kernel;
+ * DFMI_ERR_NOT_IMPLEMENTED "query compiler: too many literals" past that); the
+ * values and errors are those of the general form. One flag bit, no struct
+ * change, no new entry point: DFMI_ABI_VERSION stays 4. */
+
 /* Signature of a built-in scalar function, for a binding's
  * SchemaProvider::get_function_meta (sqlplanner.rs:330-350 casts each
  * argument to arg_types[i]). Returns 0 and fills *num_args, *return_type and
