@@ -38,6 +38,7 @@ DFMI_FLAG_EXT_AGG_AVG = 0x80
 DFMI_FLAG_EXT_UTF8_ORDER = 0x100  # with DFMI_FLAG_EXT_UTF8_COMPARE: Utf8 <, <=, >, >=
 DFMI_FLAG_EXT_AGG_MINMAX_ANY = 0x200  # with DFMI_FLAG_EXT_AGGREGATE: MIN / MAX over a Boolean or Utf8 argument
 DFMI_FLAG_EXT_MODULUS = 0x400  # the Modulus operator (%) over the integer and float types
+DFMI_FLAG_EXT_CAST_ANY = 0x800  # with DFMI_FLAG_EXT_CAST: CAST of a Utf8 column (parsed), Boolean <-> numeric
 
 # dfmi_agg_fn (AggregateType, expression.rs:33-40)
 DFMI_AGG_MIN = 0

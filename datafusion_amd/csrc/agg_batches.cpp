@@ -53,6 +53,8 @@ struct Failure {
 
 Fail device_fail(int kind) {
     if (kind == ERRK_DIV_ZERO) return Fail{DFMI_ERR_DIVIDE_BY_ZERO, "DivideByZero"};
+    if (is_cast_digits(kind))
+        return Fail{DFMI_ERR_NOT_IMPLEMENTED, cast_digits_message(kind)};
     return Fail{DFMI_ERR_PANIC, kind == ERRK_REM_OVERFLOW ? "attempt to calculate the remainder with overflow"
                                                           : "attempt to divide with overflow"};
 }

@@ -602,6 +602,8 @@ extern "C" int32_t dfmi_aggregate_batch(dfmi_context* ctx, dfmi_agg_state* st, c
         else if (dev_kind && (!se.set || dev_key < se.key))
             fail = dev_kind == ERRK_DIV_ZERO
                        ? Fail{DFMI_ERR_DIVIDE_BY_ZERO, "DivideByZero"}
+                   : (is_cast_digits(dev_kind))
+                       ? Fail{DFMI_ERR_NOT_IMPLEMENTED, cast_digits_message(dev_kind)}
                        : Fail{DFMI_ERR_PANIC, dev_kind == ERRK_REM_OVERFLOW
                                                   ? "attempt to calculate the remainder with overflow"
                                                   : "attempt to divide with overflow"};

@@ -270,7 +270,15 @@ int compile_node(const Builder& b, int t, const dfmi_schema& s, uint32_t flags, 
                 // extension: CAST of a column / expression (expression.rs:281-290)
                 const int c = compile_node(b, inner, s, flags, p);
                 const int from = p.ir[c].type;
-                if (!is_numeric_type(from) || !is_numeric_type(n.data_type))
+                // DFMI_FLAG_EXT_CAST_ANY: a Utf8 column parsed into Boolean or a number,
+                // Boolean -> a number, a number -> Boolean
+                const int to = n.data_type;
+                const bool any = (flags & DFMI_FLAG_EXT_CAST_ANY) &&
+                                 ((from == DFMI_TYPE_UTF8 && p.ir[c].kind == IR_COL &&
+                                   (to == DFMI_TYPE_BOOLEAN || is_numeric_type(to))) ||
+                                  (from == DFMI_TYPE_BOOLEAN && is_numeric_type(to)) ||
+                                  (is_numeric_type(from) && to == DFMI_TYPE_BOOLEAN));
+                if (!any && (!is_numeric_type(from) || !is_numeric_type(to)))
                     throw CompileError{DFMI_ERR_NOT_IMPLEMENTED, std::string("CAST from ") + type_debug(from) +
                                                                      " to " + type_debug(n.data_type)};
                 ir.kind = IR_CAST;

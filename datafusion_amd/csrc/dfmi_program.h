@@ -10,7 +10,8 @@
 namespace dfmi {
 
 // IR_CAST (DFMI_FLAG_EXT_CAST): child l converted to `type` with the arrow
-// cast kernel's rules; IR_ISNULL (DFMI_FLAG_EXT_IS_NULL): op 0 = IS NULL,
+// cast kernel's rules (DFMI_FLAG_EXT_CAST_ANY: l may be a Utf8 column, parsed,
+// or Boolean, or `type` Boolean); IR_ISNULL (DFMI_FLAG_EXT_IS_NULL): op 0 = IS NULL,
 // 1 = IS NOT NULL of child l; IR_FN (DFMI_FLAG_EXT_SCALAR_FUNCTIONS): built-in
 // function `fn` (a row of compile.cpp's registry) of child l, or of l and r.
 enum IrKind { IR_COL = 1, IR_LIT = 2, IR_BIN = 3, IR_CAST = 4, IR_ISNULL = 5, IR_FN = 6 };

@@ -692,6 +692,8 @@ extern "C" int32_t dfmi_filter_project(dfmi_context* ctx, const dfmi_program* pr
             if (dev_kind == ERRK_DIV_ZERO) throw Fail{DFMI_ERR_DIVIDE_BY_ZERO, "DivideByZero"};
             if (dev_kind == ERRK_REM_OVERFLOW)
                 throw Fail{DFMI_ERR_PANIC, "attempt to calculate the remainder with overflow"};
+            if (is_cast_digits(dev_kind))
+                throw Fail{DFMI_ERR_NOT_IMPLEMENTED, cast_digits_message(dev_kind)};
             throw Fail{DFMI_ERR_PANIC, "attempt to divide with overflow"};
         }
         if (se.set) {
@@ -1024,6 +1026,8 @@ int32_t dfmi::filter_project_batches_staged(dfmi_context* ctx, const dfmi_progra
                 if (kind == ERRK_DIV_ZERO) throw Fail{DFMI_ERR_DIVIDE_BY_ZERO, "DivideByZero"};
                 if (kind == ERRK_REM_OVERFLOW)
                     throw Fail{DFMI_ERR_PANIC, "attempt to calculate the remainder with overflow"};
+                if (is_cast_digits(kind))
+                    throw Fail{DFMI_ERR_NOT_IMPLEMENTED, cast_digits_message(kind)};
                 throw Fail{DFMI_ERR_PANIC, "attempt to divide with overflow"};
             }
             const int64_t n = ins[b].num_rows;

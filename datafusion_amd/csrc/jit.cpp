@@ -72,6 +72,9 @@ bool is_signed_int(int t) { return t >= DFMI_TYPE_INT8 && t <= DFMI_TYPE_INT64; 
 // Casts num::cast can never reject: int -> float, Float32 -> Float64, and an
 // integer into a type holding all of its values.
 bool cast_total(int from, int to) {
+    // DFMI_FLAG_EXT_CAST_ANY: Boolean <-> numeric always fits, a string may not parse
+    if (from == DFMI_TYPE_UTF8) return false;
+    if (from == DFMI_TYPE_BOOLEAN || to == DFMI_TYPE_BOOLEAN) return true;
     if (is_float(to)) return !is_float(from) || type_width(from) <= type_width(to);
     if (is_float(from)) return false;
     const int wf = type_width(from), wt = type_width(to);
@@ -250,6 +253,31 @@ struct Gen {
             const int from = p->ir[n.l].type, to = n.type;
             if (from == to) return a;
             const std::string v = t();
+            if (from == DFMI_TYPE_UTF8) {
+                // DFMI_FLAG_EXT_CAST_ANY: the column's bytes parsed (str::parse); what
+                // does not parse is a null. Shaped like the Divide arm: the limit
+                // report for evaluated, non-null rows, then the value.
+                const std::string ct = to == DFMI_TYPE_BOOLEAN ? "bool" : ctype(to);
+                const int u = X.slot_of_utf8(p->ir[n.l].col);
+                o << "    " << ct << " " << v << ";\n    bool " << v << "_l = false;\n"
+                  << "    const bool " << v << "_n = (" << act << ")" << (a.n != "true" ? " && (" + a.n + ")" : "")
+                  << " && dfmi::utf8_parse<" << ct << ">(A, " << u << ", row, " << v << ", " << v << "_l);\n";
+                if (is_float(to))
+                    o << "    if (" << v << "_l) dfmi::report_err(A.err, " << ord_base + n.ordinal
+                      << ", row, dfmi::ERRK_CAST_DIGITS" << (to == DFMI_TYPE_FLOAT32 ? "_F32" : "") << ");\n";
+                o << "    if (!" << v << "_n) " << v << " = (" << ct << ")0;\n";
+                return Val{v, v + "_n"};
+            }
+            if (from == DFMI_TYPE_BOOLEAN) {  // true -> 1, false -> 0; a null stays a null (zero slot)
+                o << "    const " << ctype(to) << " " << v << " = (" << ctype(to) << ")((" << (a.n != "true" ? "(" + a.n + ") && " : "")
+                  << "(" << a.v << ")) ? 1 : 0);\n";
+                return Val{v, a.n};
+            }
+            if (to == DFMI_TYPE_BOOLEAN) {  // x != 0: NaN is true, -0.0 false
+                o << "    const bool " << v << " = " << (a.n != "true" ? "(" + a.n + ") && " : "") << "((" << a.v
+                  << ") != (" << ctype(from) << ")0);\n";
+                return Val{v, a.n};
+            }
             o << "    " << ctype(to) << " " << v << ";\n";
             if (cast_total(from, to)) {
                 o << "    (void)dfmi::num_cast<" << ctype(to) << ">(" << a.v << ", " << v << ");\n";
@@ -1527,6 +1555,13 @@ hipFunction_t get_kernel(int device, const Plan& P, Launch& X, double* compile_m
         fprintf(stderr, "%s\n", src.c_str() + std::min(src.size(), src.find(skeleton_text()) + skeleton_text().size()));
     ShapeHit h;
     std::shared_ptr<Compiled> c = compile(device, src, X.kname, compile_ms);
+    if (!(X.waves_soft && X.waves_per_eu > 0) && getenv("DFMI_JIT_VERBOSE")) {  // (tools/*_probe.py read this line)
+        int scratch = 0, regs = 0;
+        (void)hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, c->fn);
+        (void)hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, c->fn);
+        fprintf(stderr, "dfmi jit: %s waves_per_eu %d: scratch %d B/lane, %d VGPRs\n", X.kname.c_str(), X.waves_per_eu,
+                scratch, regs);
+    }
     if (X.waves_soft && X.waves_per_eu > 0) {
         // a soft occupancy hint: if the register allocator had to spill more
         // than a little to meet it, the query shape is compiled again without

@@ -105,7 +105,10 @@ enum ErrKind : unsigned {
     ERRK_DIV_OVERFLOW = 2,
     ERRK_LOOKBACK_TIMEOUT = 3,
     ERRK_CAPACITY = 4,
-    ERRK_REM_OVERFLOW = 5  // Modulus: iN::MIN % -1 (the kind field of report_err's key has 4 bits)
+    ERRK_REM_OVERFLOW = 5,  // Modulus: iN::MIN % -1 (the kind field of report_err's key has 4 bits)
+    // CAST of a string to Float64 / Float32: more than 19 significant digits decide the rounding
+    ERRK_CAST_DIGITS = 6,
+    ERRK_CAST_DIGITS_F32 = 7
 };
 
 constexpr u64 FLAG_A = 1ull << 62;
@@ -522,6 +525,422 @@ __device__ __forceinline__ bool num_cast(From x, To& out) {
         }
         out = (To)x;
         return true;
+    }
+}
+
+// ---- utf8 parse helpers: begin ---------------------------------------------
+// CAST from Utf8 (DFMI_FLAG_EXT_CAST_ANY): Rust's str::parse for bool, iN / uN,
+// f32 and f64 as csv_reader.cpp restates it (parse_int, parse_float, the
+// Boolean rule) -- a string the reader would report a parse error for is a
+// null. Plain C++ between the two markers, no Args and no wave intrinsics:
+// tests/native/cast_parse_driver.cpp compiles this very text for the host (it
+// defines DFMI_PARSE_FN, DFMI_PARSE_OUTLINE and the integer typedefs) and
+// checks it against std::from_chars / strtof under the sanitizers.
+#ifndef DFMI_PARSE_FN
+#define DFMI_PARSE_FN __device__ __forceinline__
+#define DFMI_PARSE_OUTLINE __device__ __noinline__
+#endif
+
+// What a parse gives: st 0 a null, 1 the value's bits, 2 the program limit of
+// the float parser (more than 19 significant digits decide the rounding).
+struct ParseRes {
+    u64 bits;
+    unsigned st;
+};
+
+// ASCII letters only differ from their lower case in bit 5, and no other byte
+// maps onto a letter by setting it.
+DFMI_PARSE_FN bool parse_word(const u8* p, int len, const char* w, int n) {
+    if (len != n) return false;
+    for (int i = 0; i < n; ++i)
+        if ((u8)(p[i] | 0x20) != (u8)w[i]) return false;
+    return true;
+}
+
+// bool::from_str with the reader's letter-case rule: true / false, any case.
+DFMI_PARSE_FN ParseRes parse_bool(const u8* p, int len) {
+    const char t[] = {'t', 'r', 'u', 'e'}, f[] = {'f', 'a', 'l', 's', 'e'};
+    if (parse_word(p, len, t, 4)) return ParseRes{1, 1};
+    return ParseRes{0, parse_word(p, len, f, 5) ? 1u : 0u};
+}
+
+// iN / uN::from_str: [+-] (a '-' only for signed targets), then digits only,
+// at least one, the value inside the target's range. One body for the eight
+// integer types; bits: the value sign-extended to 64 bits.
+DFMI_PARSE_OUTLINE ParseRes parse_int(const u8* p, int len, bool is_signed, int width) {
+    int i = 0;
+    bool neg = false;
+    if (len > 0 && (p[0] == '+' || p[0] == '-')) {
+        neg = p[0] == '-';
+        if (neg && !is_signed) return ParseRes{0, 0};
+        i = 1;
+    }
+    if (i >= len) return ParseRes{0, 0};
+    const u64 tmax = ~0ull >> (64 - width + (is_signed ? 1 : 0));
+    const u64 lim = neg ? tmax + 1 : tmax;  // |MIN| = MAX + 1
+    const u64 q = lim / 10, r = lim % 10;
+    u64 acc = 0;
+    for (; i < len; ++i) {
+        const unsigned d = (unsigned)p[i] - (unsigned)'0';
+        if (d > 9) return ParseRes{0, 0};
+        if (acc > q || (acc == q && d > r)) return ParseRes{0, 0};  // out of range (a wrong byte later: a null too)
+        acc = acc * 10 + d;
+    }
+    return ParseRes{neg ? 0 - acc : acc, 1};
+}
+
+// The decimal a float string spells: (-1)^neg * [w, w + more) * 10^e, w the
+// first 19 digits of the digit string without its leading zeros (19: the
+// most that always fit 64 bits), `more` = some digit past them is nonzero;
+// e is clamped to +-400, past every finite double either way.
+struct ParseDec {
+    u64 w;
+    int e;
+    int kind;  // 0: no number; 1: the decimal; 2: inf; 3: nan
+    bool neg, more;
+};
+
+DFMI_PARSE_FN ParseDec parse_scan(const u8* p, int len) {
+    ParseDec D{0, 0, 0, false, false};
+    int i = 0;
+    if (len > 0 && (p[0] == '+' || p[0] == '-')) {
+        D.neg = p[0] == '-';
+        i = 1;
+    }
+    const char inf[] = {'i', 'n', 'f', 'i', 'n', 'i', 't', 'y'}, nan[] = {'n', 'a', 'n'};
+    if (parse_word(p + i, len - i, inf, 3) || parse_word(p + i, len - i, inf, 8)) {
+        D.kind = 2;
+        return D;
+    }
+    if (parse_word(p + i, len - i, nan, 3)) {
+        D.kind = 3;
+        return D;
+    }
+    int taken = 0;   // digits in w
+    i64 digits = 0;  // digits seen
+    i64 adj = 0;     // exponent from the point's position and the digits not in w
+    bool point = false;
+    for (; i < len; ++i) {
+        const u8 c = p[i];
+        if (c == '.' && !point) {
+            point = true;
+            continue;
+        }
+        const unsigned d = (unsigned)c - (unsigned)'0';
+        if (d > 9) break;
+        ++digits;
+        if (taken == 0 && d == 0) {  // a leading zero
+            adj -= point ? 1 : 0;
+        } else if (taken < 19) {
+            D.w = D.w * 10 + d;
+            ++taken;
+            adj -= point ? 1 : 0;
+        } else {
+            D.more = D.more || d != 0;
+            adj += point ? 0 : 1;
+        }
+    }
+    if (!digits) return D;
+    i64 ex = 0;
+    if (i < len && (p[i] | 0x20) == 'e') {
+        ++i;
+        bool eneg = false;
+        if (i < len && (p[i] == '+' || p[i] == '-')) eneg = p[i++] == '-';
+        int ed = 0;
+        for (; i < len; ++i) {
+            const unsigned d = (unsigned)p[i] - (unsigned)'0';
+            if (d > 9) break;
+            ++ed;
+            if (ex < 4000000000ll) ex = ex * 10 + d;  // saturates: past every string's own adjustment
+        }
+        if (!ed) return D;
+        if (eneg) ex = -ex;
+    }
+    if (i != len) return D;
+    const i64 e = adj + ex;
+    D.e = e > 400 ? 400 : (e < -400 ? -400 : (int)e);
+    D.kind = 1;
+    return D;
+}
+
+template <typename T>
+struct ParseFmt;
+template <>
+struct ParseFmt<double> {
+    typedef u64 U;
+    static constexpr int P = 53, EMIN = -1022, EMAX = 1023;
+    static constexpr u64 INF = 0x7FF0000000000000ull, QNAN = 0x7FF8000000000000ull, SIGN = 1ull << 63;
+};
+template <>
+struct ParseFmt<float> {
+    typedef u32 U;
+    static constexpr int P = 24, EMIN = -126, EMAX = 127;
+    static constexpr u64 INF = 0x7F800000ull, QNAN = 0x7FC00000ull, SIGN = 1ull << 31;
+};
+
+// m * 2^x (bit 63 of m set; sticky: the true value lies strictly above it,
+// below the next m) rounded to T, nearest, ties to even; subnormals at their
+// quantum, +inf past the range. The bits of the positive result.
+template <typename T>
+DFMI_PARSE_FN u64 parse_round(u64 m, int x, bool sticky) {
+    typedef ParseFmt<T> F;
+    const int E = x + 63;  // the exponent of m's top bit
+    if (E > F::EMAX) return F::INF;
+    const int keep = E >= F::EMIN ? F::P : F::P - (F::EMIN - E);  // result bits above the rounding point
+    if (keep < 0) return 0;                                      // below half the least subnormal
+    const int drop = 64 - keep;                                  // 11 .. 64
+    u64 r = keep ? m >> drop : 0;
+    const u64 half = 1ull << (drop - 1);
+    const u64 rest = drop == 64 ? m : (m & ((1ull << drop) - 1));
+    if (rest > half || (rest == half && (sticky || (r & 1)))) ++r;
+    // a carry out of the kept bits lands in the exponent field (the top: INF)
+    if (E >= F::EMIN) return ((u64)(E - F::EMIN) << (F::P - 1)) + r;
+    return r;
+}
+
+constexpr int kParseWords = 28;  // 32-bit words of the exact path's integers (5^343 < 2^797)
+constexpr int kParseSmall = 4;   // ... and of its short form: |e| <= 27, 5^27 < 2^63, w * 5^27 < 2^127
+
+// The integers of the exact path are arrays of W 32-bit words. W = kParseSmall:
+// every loop runs over all W words (fixed trip counts: the arrays stay in
+// registers); W = kParseWords: over the words in use (the arrays are scratch).
+template <int W>
+DFMI_PARSE_FN void parse_big_mul(u32* a, int& n, u32 m) {
+    u64 c = 0;
+    const int top = W <= kParseSmall ? W : n;
+    for (int i = 0; i < top; ++i) {
+        c += (u64)a[i] * m;
+        a[i] = (u32)c;
+        c >>= 32;
+    }
+    if (W > kParseSmall && c && n < W) a[n++] = (u32)c;
+}
+
+template <int W>
+DFMI_PARSE_FN void parse_big_mul_pow5(u32* a, int& n, int k) {
+    for (; k >= 13; k -= 13) parse_big_mul<W>(a, n, 1220703125u);  // 5^13
+    u32 m = 1;
+    for (; k > 0; --k) m *= 5u;
+    parse_big_mul<W>(a, n, m);
+}
+
+// Bits of the W-word integer a (nonzero).
+template <int W>
+DFMI_PARSE_FN int parse_big_bits(const u32* a, int n) {
+    if (W > kParseSmall) return 32 * (n - 1) + 32 - __builtin_clz(a[n - 1]);
+    int L = 0;
+    for (int i = 0; i < W; ++i)
+        if (a[i]) L = 32 * i + 32 - __builtin_clz(a[i]);
+    return L;
+}
+
+// Word i of a, 0 past the array (i may be a run-time value: spelled as a
+// chain of selects for the short form, whose arrays must not be indexed).
+template <int W>
+DFMI_PARSE_FN u32 parse_big_word(const u32* a, int i) {
+    if (W > kParseSmall) return i < W ? a[i] : 0u;
+    u32 v = 0;
+    for (int j = 0; j < W; ++j) v = i == j ? a[j] : v;
+    return v;
+}
+template <int W>
+DFMI_PARSE_FN void parse_big_set(u32* a, int i, u32 v) {
+    if (W > kParseSmall) {
+        if (i < W) a[i] = v;
+        return;
+    }
+    for (int j = 0; j < W; ++j) a[j] = i == j ? v : a[j];
+}
+
+struct ParseBig {
+    u64 m;
+    int x;
+    bool sticky;
+};
+
+// w * 10^e (w > 0; |e| <= 343 for W = kParseWords, |e| <= 27 for kParseSmall)
+// as m * 2^x with bit 63 of m set and a sticky flag for what lies below m's
+// last bit: exact integer arithmetic over 32-bit words. e >= 0: the top 64
+// bits of w * 5^e. e < 0: a bit-by-bit long division of w * 2^s by 5^|e|, s
+// chosen so that the quotient has 63 or 64 bits; the remainder is the sticky
+// bit. It runs only where Clinger's fast path does not apply.
+template <int W>
+DFMI_PARSE_FN ParseBig parse_big_w(u64 w, int e) {
+    ParseBig B{0, 0, false};
+    if (e >= 0) {
+        u32 a[W];
+        for (int i = 0; i < W; ++i) a[i] = 0;
+        a[0] = (u32)w;
+        a[1] = (u32)(w >> 32);
+        int n = a[1] ? 2 : 1;
+        parse_big_mul_pow5<W>(a, n, e);
+        const int L = parse_big_bits<W>(a, n);
+        if (L <= 64) {
+            const u64 v = (u64)a[0] | ((u64)a[1] << 32);
+            B.m = v << (64 - L);
+            B.x = e - (64 - L);
+            return B;
+        }
+        const int sh = L - 64, wi = sh >> 5, bi = sh & 31;  // the bits [sh, sh + 64)
+        const u32 a0 = parse_big_word<W>(a, wi);
+        const u64 lo = (u64)a0 | ((u64)parse_big_word<W>(a, wi + 1) << 32);
+        B.m = bi ? (lo >> bi) | ((u64)parse_big_word<W>(a, wi + 2) << (64 - bi)) : lo;
+        B.sticky = (a0 & ((1u << bi) - 1u)) != 0;
+        for (int i = 0; i < (W <= kParseSmall ? W : wi); ++i) B.sticky = B.sticky || (i < wi && a[i] != 0);
+        B.x = e + sh;
+        return B;
+    }
+    u32 d[W], r[W];
+    for (int i = 0; i < W; ++i) d[i] = r[i] = 0;
+    d[0] = 1;
+    int nd = 1;
+    parse_big_mul_pow5<W>(d, nd, -e);
+    const int bd = parse_big_bits<W>(d, nd), bw = 64 - __builtin_clzll(w);
+    if (W <= kParseSmall) nd = (bd + 31) >> 5;
+    // numerator w * 2^s, s = bd + 63 - bw: its top bd - 1 bits are below the
+    // divisor and start the remainder, the 64 bits after them give the quotient
+    const int t = bd - 1 - bw;
+    int feed = 0;  // bits of w not yet in the remainder
+    if (t >= 0) {
+        const int wi = t >> 5, bi = t & 31;
+        const u64 lo = w << bi, hi = bi ? w >> (64 - bi) : 0;
+        parse_big_set<W>(r, wi, (u32)lo);
+        parse_big_set<W>(r, wi + 1, (u32)(lo >> 32));
+        parse_big_set<W>(r, wi + 2, (u32)hi);
+    } else {
+        feed = -t;  // <= 62
+        const u64 v = w >> feed;
+        r[0] = (u32)v;
+        r[1] = (u32)(v >> 32);
+    }
+    // the remainder is below 2 * divisor: one word more than the divisor at most
+    const int nr = W <= kParseSmall ? W : (nd + 1 < W ? nd + 1 : W);
+    u64 q = 0;
+    for (int step = 0; step < 64; ++step) {
+        u32 c = 0;
+        if (feed > 0) c = (u32)((w >> --feed) & 1);
+        for (int i = 0; i < nr; ++i) {
+            const u32 v = r[i];
+            r[i] = (v << 1) | c;
+            c = v >> 31;
+        }
+        bool ge = true;  // r >= d, from the top word down (words past either number are zero)
+        for (int i = nr - 1; i >= 0; --i)
+            if (r[i] != d[i]) {
+                ge = r[i] > d[i];
+                break;
+            }
+        q <<= 1;
+        if (ge) {
+            q |= 1;
+            u32 b = 0;
+            for (int i = 0; i < nr; ++i) {
+                const u64 v = (u64)r[i] - (u64)d[i] - b;
+                r[i] = (u32)v;
+                b = (u32)(v >> 63);
+            }
+        }
+    }
+    for (int i = 0; i < nr; ++i) B.sticky = B.sticky || r[i] != 0;
+    B.x = e - (bd + 63 - bw);
+    if (!(q >> 63)) {  // 63 quotient bits
+        q <<= 1;
+        B.x -= 1;
+    }
+    B.m = q;
+    return B;
+}
+
+// Out of line, as irem_word is: the long form is ~26 words a step. The short
+// form serves the machine-written case -- 16 or 17 digits with a small
+// exponent, repr() of a double -- which the fast path cannot take (w >= 2^53).
+DFMI_PARSE_OUTLINE ParseBig parse_big(u64 w, int e) { return parse_big_w<kParseWords>(w, e); }
+DFMI_PARSE_OUTLINE ParseBig parse_big_small(u64 w, int e) { return parse_big_w<kParseSmall>(w, e); }
+DFMI_PARSE_FN ParseBig parse_exact(u64 w, int e) {
+    return e >= -27 && e <= 27 ? parse_big_small(w, e) : parse_big(w, e);
+}
+
+// w * 10^e (w > 0) correctly rounded to T: Clinger's fast path -- w and 10^|e|
+// both exact in T, one IEEE multiply or divide (-ffp-contract=off) -- or the
+// exact path. (Overloads on a value of the target type.)
+DFMI_PARSE_FN u64 parse_dec(u64 w, int e, double) {
+    if (!(w >> 53) && e >= -22 && e <= 22) {
+        const double p10[] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
+                              1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+        const double v = e < 0 ? (double)w / p10[-e] : (double)w * p10[e];
+        return __builtin_bit_cast(u64, v);
+    }
+    if (e > 309) return ParseFmt<double>::INF;
+    if (e < -343) return 0;  // w < 10^19: below 10^-324, under half the least subnormal
+    const ParseBig B = parse_exact(w, e);
+    return parse_round<double>(B.m, B.x, B.sticky);
+}
+DFMI_PARSE_FN u64 parse_dec(u64 w, int e, float) {
+    if (!(w >> 24) && e >= -10 && e <= 10) {
+        const float p10[] = {1e0f, 1e1f, 1e2f, 1e3f, 1e4f, 1e5f, 1e6f, 1e7f, 1e8f, 1e9f, 1e10f};
+        const float v = e < 0 ? (float)w / p10[-e] : (float)w * p10[e];
+        return (u64)__builtin_bit_cast(u32, v);
+    }
+    if (e > 309) return ParseFmt<float>::INF;
+    if (e < -343) return 0;
+    const ParseBig B = parse_exact(w, e);
+    return parse_round<float>(B.m, B.x, B.sticky);  // from the exact value: one rounding
+}
+
+// f32 / f64::from_str. Digits past the 19th only say "the value lies strictly
+// between w * 10^e and (w + 1) * 10^e": where both round to one float that is
+// the result, where they differ the row reaches the program limit (st 2).
+template <typename T>
+DFMI_PARSE_OUTLINE ParseRes parse_float(const u8* p, int len) {
+    typedef ParseFmt<T> F;
+    const ParseDec D = parse_scan(p, len);
+    if (!D.kind) return ParseRes{0, 0};
+    u64 b = 0;
+    if (D.kind == 2) {
+        b = F::INF;
+    } else if (D.kind == 3) {
+        b = F::QNAN;
+    } else if (D.w) {
+        b = parse_dec(D.w, D.e, (T)0);
+        if (D.more && parse_dec(D.w + 1, D.e, (T)0) != b) return ParseRes{0, 2};
+    }
+    return ParseRes{D.neg ? b | F::SIGN : b, 1};
+}
+// ---- utf8 parse helpers: end -----------------------------------------------
+
+// The value of row `row` of Utf8 column u parsed as T (bool, an integer type,
+// float or double): false for a null (`out` zero); `limit` where the float
+// parser's program limit is reached. Only the row's own bytes are read, one
+// at a time: nothing before bytes + offs[0], nothing past offs[n_rows],
+// whatever the base's alignment. Rows past n_rows read nothing.
+template <typename T>
+struct ParseTarget {
+    static constexpr int kind = (T)0.5 == (T)0 ? 0 : 1;  // integer / float
+};
+template <>
+struct ParseTarget<bool> {
+    static constexpr int kind = 2;
+};
+template <typename T>
+__device__ __forceinline__ bool utf8_parse(const Args& A, int u, i64 row, T& out, bool& limit) {
+    out = (T)0;
+    limit = false;
+    if (row >= A.n_rows) return false;
+    const int s = A.offs[u][row], e = A.offs[u][row + 1];
+    const u8* p = A.bytes[u] + s;
+    if constexpr (ParseTarget<T>::kind == 2) {
+        const ParseRes r = parse_bool(p, e - s);
+        out = r.bits != 0;
+        return r.st == 1;
+    } else if constexpr (ParseTarget<T>::kind == 0) {
+        const ParseRes r = parse_int(p, e - s, (T)-1 < (T)0, 8 * (int)sizeof(T));
+        if (r.st == 1) out = (T)r.bits;
+        return r.st == 1;
+    } else {
+        const ParseRes r = parse_float<T>(p, e - s);
+        if (r.st == 1) out = __builtin_bit_cast(T, (typename ParseFmt<T>::U)r.bits);
+        limit = r.st == 2;
+        return r.st == 1;
     }
 }
 

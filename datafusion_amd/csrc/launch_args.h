@@ -10,6 +10,14 @@
 #include "jit_skeleton.hip"
 
 namespace dfmi {
+
+// The text of ERRK_CAST_DIGITS / ERRK_CAST_DIGITS_F32 (DFMI_FLAG_EXT_CAST_ANY).
+inline const char* cast_digits_message(int kind) {
+    return kind == ERRK_CAST_DIGITS_F32 ? "device program limit: CAST to Float32 needs more than 19 significant digits"
+                                        : "device program limit: CAST to Float64 needs more than 19 significant digits";
+}
+inline bool is_cast_digits(int kind) { return kind == ERRK_CAST_DIGITS || kind == ERRK_CAST_DIGITS_F32; }
+
 namespace xi {
 
 // The numeric and Utf8 input columns of X's slots.

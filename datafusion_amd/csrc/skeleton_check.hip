@@ -1,7 +1,8 @@
 // Build-time check of jit_skeleton.hip: instantiates every skeleton template
 // with a representative generated body (one Float64 predicate, a gathered
 // column, a Utf8 gather, integer division at several widths, the remainder
-// helpers at every width, every scalar function helper), so a broken skeleton fails `make` rather than the
+// helpers at every width, every scalar function helper, every target of the Utf8
+// parsers), so a broken skeleton fails `make` rather than the
 // first query compile on the GPU. Not linked into libdfmi.so.
 #include <hip/hip_runtime.h>
 
@@ -84,6 +85,27 @@ extern "C" __global__ __launch_bounds__(512) void dfmi_skeleton_check(const dfmi
                       (u64)dfmi::irem_lit<i16>((i16)x, (i16)y, m) + dfmi::irem_lit<u16>((u16)x, (u16)y, m) +
                       (u64)dfmi::irem_lit<i8>((i8)x, (i8)y, m) + dfmi::irem_lit<u8>((u8)x, (u8)y, m);
         dfmi::report_err(A.err, 2, base, dfmi::ERRK_REM_OVERFLOW);
+    }
+    // CAST from Utf8 (DFMI_FLAG_EXT_CAST_ANY): every target's parser through the per-row fetch
+    {
+        bool lim = false, l2 = false, pb = false;
+        i8 a8; i16 a16; i32 a32; i64 a64; u8 b8; u16 b16; u32 b32; u64 b64; float pf; double pd;
+        const i64 row = base + tid;
+        u64 acc = 0;
+        acc += dfmi::utf8_parse<i8>(A, 0, row, a8, l2) ? (u64)a8 : 1;
+        acc += dfmi::utf8_parse<i16>(A, 0, row, a16, l2) ? (u64)a16 : 1;
+        acc += dfmi::utf8_parse<i32>(A, 0, row, a32, l2) ? (u64)a32 : 1;
+        acc += dfmi::utf8_parse<i64>(A, 0, row, a64, l2) ? (u64)a64 : 1;
+        acc += dfmi::utf8_parse<u8>(A, 0, row, b8, l2) ? (u64)b8 : 1;
+        acc += dfmi::utf8_parse<u16>(A, 0, row, b16, l2) ? (u64)b16 : 1;
+        acc += dfmi::utf8_parse<u32>(A, 0, row, b32, l2) ? (u64)b32 : 1;
+        acc += dfmi::utf8_parse<u64>(A, 0, row, b64, l2) ? b64 : 1;
+        acc += dfmi::utf8_parse<bool>(A, 0, row, pb, l2) ? (u64)pb : 2;
+        acc += dfmi::utf8_parse<float>(A, 1, row, pf, l2) ? (u64)__builtin_bit_cast(u32, pf) : 3;
+        if (l2) dfmi::report_err(A.err, 3, row, dfmi::ERRK_CAST_DIGITS_F32);
+        acc += dfmi::utf8_parse<double>(A, 1, row, pd, lim) ? dfmi::bits(pd) : 4;
+        if (lim) dfmi::report_err(A.err, 3, row, dfmi::ERRK_CAST_DIGITS);
+        if (row < A.n_rows) ((u64*)A.out[3])[row] = acc;
     }
     // scalar function extension: every helper, Float64 and Float32
     {

@@ -352,6 +352,61 @@ typedef struct dfmi_expr_node {
  * values and errors are those of the general form. One flag bit, no struct
  * change, no new entry point: DFMI_ABI_VERSION stays 4. */
 
+#define DFMI_FLAG_EXT_CAST_ANY     0x800u
+/* The rest of CAST, effective only together with DFMI_FLAG_EXT_CAST (as
+ * UTF8_ORDER is with UTF8_COMPARE): without both flags every expression
+ * compiles and fails exactly as before, and the generated code of a shape
+ * without such a cast does not change with the flag. Build-defined, parity
+ * unpinned: the reference executes no CAST of a column.
+ *   forms:    CAST(e AS T), e not a literal, where (a) e is a Utf8 COLUMN and T
+ *             is Boolean, Int8..Int64, UInt8..UInt64, Float32 or Float64; or
+ *             (b) e is Boolean and T numeric; or (c) e is numeric and T
+ *             Boolean. The name is "CAST(#i AS Type)" as for the numeric casts.
+ *             Left out, with their NotImplemented("CAST from .. to ..") text
+ *             unchanged: T = Utf8 (numeric -> Utf8 needs computed Utf8 outputs
+ *             and shortest float formatting), Utf8 -> Utf8, a Utf8 literal
+ *             child; Boolean = / < comparisons stay comparison_ops errors;
+ *   nulls:    arrow's cast rule, as for the numeric casts: a null input gives
+ *             a null, a value the target cannot hold -- a string that does not
+ *             parse -- becomes a null with value slot zero; no cast raises an
+ *             error but the one program limit below. After a Selection the
+ *             columns are all-valid and a null slot is parsed by its raw bytes
+ *             (the rule of Utf8 `=`), in practice "", which is a null;
+ *   Boolean:  true -> 1, false -> 0 (1.0 / 0.0); numeric -> Boolean is x != 0,
+ *             so NaN is true and -0.0 false, never null for a valid input;
+ *   strings:  a cast of a string gives what the native CSV reader
+ *             (dfmi_csv_*) gives for a field with that text -- Rust's
+ *             str::parse -- and a null where the reader reports a parse error:
+ *             integers: [+-] (a '-' only for signed targets: "-0" to an
+ *               unsigned type is null), then ASCII digits only, at least one;
+ *               no blanks, '.', exponent, '_', non-ASCII digits; a NUL byte is
+ *               a wrong byte; any number of leading zeros; out of range: null;
+ *             Boolean: "true" / "false" in any ASCII letter case;
+ *             floats: [+-], then inf / infinity / nan in any case, or digits
+ *               with an optional '.' (at least one digit overall) and an
+ *               optional e|E [+-] digits (any length, saturating). nan is the
+ *               positive quiet NaN (0x7FF8.. / 0x7FC00000), -nan its negation.
+ *               Otherwise the decimal value correctly rounded (nearest, ties
+ *               to even) directly to the target width -- Float32 is not
+ *               rounded through Float64 -- subnormals at their quantum, +-inf
+ *               beyond the range (not null), +-0 with the sign kept below half
+ *               the least subnormal;
+ *   limit:    the digit string without its leading zeros is read through its
+ *             first 19 digits (the most that always fit 64 bits); later digits
+ *             only count as "some dropped digit is nonzero". If none is, the
+ *             value is exact. Otherwise it lies strictly between w * 10^e and
+ *             (w + 1) * 10^e: where both round to one float, that is the
+ *             result; where they differ the row raises
+ *             DFMI_ERR_NOT_IMPLEMENTED "device program limit: CAST to Float64
+ *             needs more than 19 significant digits" ("Float32" likewise) at
+ *             the node's ordinal, for evaluated non-null rows only, the first
+ *             error by (ordinal, row) winning as for Divide. Machine-written
+ *             floats have at most 17 digits and never reach it;
+ *   where:    wherever a numeric CAST runs -- predicates, projections,
+ *             aggregate arguments, GROUP BY / ORDER BY key expressions; every
+ *             batch form; sliced arrays.
+ * One flag bit, no struct change, no new entry point: DFMI_ABI_VERSION stays 4. */
+
 /* Signature of a built-in scalar function, for a binding's
  * SchemaProvider::get_function_meta (sqlplanner.rs:330-350 casts each
  * argument to arg_types[i]). Returns 0 and fills *num_args, *return_type and
