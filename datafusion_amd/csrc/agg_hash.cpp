@@ -307,6 +307,7 @@ bool use_buckets(const dfmi_agg_state* st, const HashDev& H, int64_t m, uint64_t
 }
 
 std::atomic<long> g_bucketed_batches{0};  // diagnostics: dfmi_internal_group_bucketed_batches
+std::atomic<long> g_normalize_trips{0};   // diagnostics: dfmi_internal_group_normalize_trips
 
 void accumulate_bucketed(dfmi_context* ctx, dfmi_agg_state* st, HashDev& H, const std::vector<dfmi::gb::Col>& cols,
                          int64_t m, uint64_t ng, uint32_t epoch) {
@@ -380,6 +381,26 @@ void accumulate_bucketed(dfmi_context* ctx, dfmi_agg_state* st, HashDev& H, cons
 }  // namespace
 
 long bucketed_batches() { return g_bucketed_batches.load(); }
+long normalize_trips() { return g_normalize_trips.load(std::memory_order_relaxed); }
+
+// Diagnostics (dfmi_internal_group_records): the device records of groups
+// [g0, g0 + ng) copied out as they stand -- nothing normalised, the table left
+// as it is. info: the record's words, the groups the table holds, the float
+// SUMs, then each one's digit offset in a record (3 + gb::kMaxAggs entries).
+void read_records(dfmi_context* ctx, dfmi_agg_state* st, uint64_t g0, uint64_t ng, uint64_t* out, int64_t* info) {
+    for (int i = 0; i < 3 + dfmi::gb::kMaxAggs; ++i) info[i] = 0;
+    if (!st->hd) return;
+    const HashDev& H = *st->hd;
+    info[0] = H.words;
+    info[1] = (int64_t)H.ngroups;
+    info[2] = (int64_t)H.foff.size();
+    for (size_t f = 0; f < H.foff.size(); ++f) info[3 + f] = H.foff[f];
+    if (!out || !ng) return;
+    if (g0 > H.ngroups || ng > H.ngroups - g0) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "groups past the table's"};
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(out, H.records() + g0 * (uint64_t)H.words, ng * (size_t)H.words * 8, hipMemcpyDeviceToHost));
+}
 
 // A batch merged on the host, row by row (diagnostics: DFMI_DIAG=1
 // DFMI_GROUP_HOST=1, the A/B of the device hash table).
@@ -593,7 +614,8 @@ void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<
         H.arena_cap = want;
     }
     // exact-sum digits absorb 2^31 rows between carry normalisations
-    if (!H.foff.empty() && H.rows_since_norm + (uint64_t)m > (1ull << 30)) {
+    if (!H.foff.empty() && H.rows_since_norm + (uint64_t)m > group_norm_rows(diag)) {
+        g_normalize_trips.fetch_add(1, std::memory_order_relaxed);
         HIP_TRY(dfmi::gb::launch_normalize(H.records(), H.words, H.foff.data(), (int)H.foff.size(), H.ngroups, stream));
         H.rows_since_norm = 0;
     }

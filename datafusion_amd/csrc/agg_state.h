@@ -2,6 +2,7 @@
 // and what the device hash table's driver (agg_hash.cpp) offers the entry
 // points (aggregate.cpp).
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <memory>
@@ -154,7 +155,12 @@ struct AggDiag {
     const char* subtiles = nullptr;         // DFMI_AGG_SUBTILES
     const char* rows_per_thread = nullptr;  // DFMI_ROWS_PER_THREAD
     const char* proj_dense = nullptr;       // DFMI_PROJ_DENSE
+    const char* group_norm_rows = nullptr;  // DFMI_GROUP_NORM_ROWS
 };
+
+// Rows a grouped state's exact-sum digits absorb between two carry
+// normalisations (accumulate_hashed).
+constexpr uint64_t kGroupNormRows = 1ull << 30;
 
 inline AggDiag agg_diag() {
     AggDiag d;
@@ -168,7 +174,17 @@ inline AggDiag agg_diag() {
     d.subtiles = getenv("DFMI_AGG_SUBTILES");
     d.rows_per_thread = getenv("DFMI_ROWS_PER_THREAD");
     d.proj_dense = getenv("DFMI_PROJ_DENSE");
+    d.group_norm_rows = getenv("DFMI_GROUP_NORM_ROWS");
     return d;
+}
+
+// DFMI_GROUP_NORM_ROWS (diagnostics): the normalisation threshold lowered to
+// its value, clamped to [0, kGroupNormRows] -- the knob never raises it; 0: a
+// carry pass before every batch that adds rows.
+inline uint64_t group_norm_rows(const AggDiag& diag) {
+    if (!diag.group_norm_rows) return kGroupNormRows;
+    const long long v = atoll(diag.group_norm_rows);
+    return v < 0 ? 0 : std::min<uint64_t>((uint64_t)v, kGroupNormRows);
 }
 
 // The sticky failure of a state: a batch has failed the query.
@@ -217,6 +233,8 @@ void emit_flat(const dfmi_agg_state* st, const FlatGroups& f, int64_t cap, dfmi_
 void emit_key_bytes_flat(const FlatGroups& f, int part, int32_t* offsets, int64_t num_offsets, uint8_t* data,
                          int64_t data_capacity, int64_t* data_length);
 long bucketed_batches();
+long normalize_trips();
+void read_records(dfmi_context* ctx, dfmi_agg_state* st, uint64_t g0, uint64_t ng, uint64_t* out, int64_t* info);
 
 // ---- agg_strext.cpp: the Utf8 MIN / MAX side structure's driver
 void strext_create(dfmi_context* ctx, dfmi_agg_state* st);  // st->sx when the state holds a Utf8 extreme

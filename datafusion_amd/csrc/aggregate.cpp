@@ -713,6 +713,19 @@ int32_t dfmi_agg_state_show_merged(dfmi_agg_state* st, const void* const* partia
 // dfmi_aggregate_batches call launches (tests/test_agg_batches_cpu.py).
 // Diagnostics: grouped batches accumulated by the bucketed passes (groupby.h) in this process.
 extern "C" long dfmi_internal_group_bucketed_batches() { return bucketed_batches(); }
+// Diagnostics: times the exact-sum digits' normalisation threshold tripped (accumulate_hashed) in this process.
+extern "C" long dfmi_internal_group_normalize_trips() { return normalize_trips(); }
+// Diagnostics: the hash table's device records of groups [g0, g0 + ng), by group id, as they stand (a carry pass
+// preserves an exact sum's value, so only the digits themselves show whether it ran over a record): out
+// [ng][words] (null: only info), info [3 + 15]: words, groups, float SUMs, their digit offsets.
+extern "C" int32_t dfmi_internal_group_records(dfmi_context* ctx, dfmi_agg_state* st, uint64_t g0, uint64_t ng,
+                                               uint64_t* out, int64_t* info, dfmi_error* err) {
+    return guarded(err, [&]() -> int32_t {
+        if (!ctx || !st || !info) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "NULL argument"};
+        read_records(ctx, st, g0, ng, out, info);
+        return DFMI_OK;
+    });
+}
 
 extern "C" int64_t dfmi_internal_agg_jit_check(const dfmi_program* pred, const dfmi_aggregate* const* aggs, int32_t n,
                                                const dfmi_batch* in, uint32_t flags, int32_t compile, char* buf,
