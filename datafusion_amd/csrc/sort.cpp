@@ -34,6 +34,9 @@ struct Scratch {
     // DFMI_DIAG=1 DFMI_SORT_PROFILE=1: device time of the last call's phases (dfmi_internal_sort_phases)
     std::vector<hipEvent_t> events;
     double phase_ms[kPhases] = {0, 0, 0, 0};
+    // the last call (dfmi_internal_sort_select): did the top-k prefilter run, and the rows the radix passes got
+    bool select_ran = false;
+    unsigned long long select_rows = 0;
     ~Scratch() {
         for (hipEvent_t e : events) (void)hipEventDestroy(e);
     }
@@ -135,6 +138,8 @@ int32_t sort_batches(dfmi_context* ctx, const dfmi_batch* in, int32_t nb, const 
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     Scratch& S = scratch(ctx);
+    S.select_ran = false;
+    S.select_rows = 0;
 
     auto finish_empty = [&]() {
         for (int j = 0; j < ncols; ++j) {
@@ -251,6 +256,8 @@ int32_t sort_batches(dfmi_context* ctx, const dfmi_batch* in, int32_t nb, const 
         have_perm = true;
         clock.mark(kPhaseSelect, st);
     }
+    S.select_ran = select;
+    S.select_rows = ns;
 
     // ---- the permutation: LSD passes, last key first
     auto pass = [&](int k, int what, int chunk, bool null_above, int end_bit) {
@@ -356,6 +363,16 @@ extern "C" int32_t dfmi_internal_sort_phases(const dfmi_context* ctx, double* ms
     if (!ctx || !ctx->sort_scratch || !ms) return DFMI_ERR_INVALID_ARGUMENT;
     const dfmi::srt::Scratch& S = *(const dfmi::srt::Scratch*)ctx->sort_scratch;
     for (int i = 0; i < dfmi::srt::kPhases; ++i) ms[i] = S.phase_ms[i];
+    return DFMI_OK;
+}
+
+// Diagnostics: which path the last dfmi_sort_batches on ctx took -- out[0] is 1 if the top-k prefilter ran,
+// out[1] the number of rows handed to the radix passes (every input row without the prefilter).
+extern "C" int32_t dfmi_internal_sort_select(const dfmi_context* ctx, uint64_t out[2]) {
+    if (!ctx || !ctx->sort_scratch || !out) return DFMI_ERR_INVALID_ARGUMENT;
+    const dfmi::srt::Scratch& S = *(const dfmi::srt::Scratch*)ctx->sort_scratch;
+    out[0] = S.select_ran ? 1 : 0;
+    out[1] = S.select_rows;
     return DFMI_OK;
 }
 

@@ -327,9 +327,11 @@ class DeviceEngine:
         progs = (C.c_void_p * max(1, len(projections)))(*[p.handle.value for p in projections])
         stream = torch.cuda.current_stream(self.device).cuda_stream  # the caller's stream (thread-local in torch)
         # `batches` rides along: the structs hold raw pointers into their
-        # buffers, so the call in flight keeps the batches alive itself
+        # buffers, so the call in flight keeps the batches alive itself -- and
+        # the compiled expressions, whose __del__ frees the programs behind
+        # the handles (a relation dropped mid-stream is their only other owner)
         return (predicate.handle if predicate is not None else None, progs, len(projections), barr, keep, nb, nout,
-                flags, stream, list(batches))
+                flags, stream, list(batches), (predicate, projections))
 
     def _host_batches_block(self, prep):
         """(block, outs) of a caller-owned call: a pinned host block of the

@@ -338,6 +338,31 @@ def test_relation_results_are_block_arrays_and_keep_inputs_alive():
         assert_same(d, r)
 
 
+def test_a_prepared_call_owns_its_compiled_expressions():
+    """A relation dropped mid-stream was the only owner of its compiled
+    expressions, and their __del__ frees the programs the worker's call still
+    reads through raw handles: the prepared call holds the expressions itself
+    (checked before it is started) and runs without the caller's references."""
+    import gc
+    import weakref
+    s, bs = make_batches([1024] * 8, seed=23, utf8=False)
+    pred_e = BinaryExpr(Column(0), Operator.Gt, Literal(Float64(0.25)))
+    proj_e = [Column(1), BinaryExpr(Column(0), Operator.Multiply, Column(2))]
+    p = compile_scalar_expr(None, pred_e, s)
+    cp = [compile_scalar_expr(None, e, s) for e in proj_e]
+    refs = [weakref.ref(e) for e in [p] + cp]
+    out_schema = Schema([Field("b", DataType.Float64, False), Field("ac", DataType.Float64, True)])
+    call = engine().filter_project_host_batches_async(p, cp, bs, 0, schema=out_schema, start=False)
+    del p, cp
+    gc.collect()
+    assert all(r() is not None for r in refs)
+    results, err = call.submit().result()
+    assert err is None and len(results) == len(bs)
+    for rb, b in zip(results, bs):
+        for d, (_, r) in zip(rb.columns, oracle_filter_project(s, b, pred_e, proj_e)):
+            assert_same(d, r)
+
+
 def test_host_results_outlive_their_context():
     """A dfmi_host_result may outlive its context (the pinned pool is shared
     by a context and the results it made): a context of its own, a 2,000-row

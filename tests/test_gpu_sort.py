@@ -109,6 +109,40 @@ def expected_order(cols, keys, limit=None):
     return order if limit is None else order[:limit]
 
 
+def rank_np(col):
+    """Per row a numpy integer whose order is the key order of the column's values: integers
+    themselves, false < true as 0 < 1, floats through total_order_key's transform on the integer view of their
+    bits, Utf8 the string's position among the column's distinct strings sorted as Python bytes."""
+    if col.t == T.Utf8:
+        vals = [bytes(s) for s in col.vals]
+        pos = {s: i for i, s in enumerate(sorted(set(vals)))}
+        return np.fromiter((pos[s] for s in vals), dtype=np.int64, count=col.n)
+    if col.t in (T.Float32, T.Float64):
+        wide = col.vals.dtype == np.float64
+        bits = col.vals.view(np.int64 if wide else np.int32)
+        low = (np.int64 if wide else np.int32)((1 << (63 if wide else 31)) - 1)
+        return np.where(bits >= 0, bits, bits ^ low)  # b < 0: -(b + top) - 1 is b with the bits below the sign flipped
+    if col.t == T.Boolean:
+        return col.vals.astype(np.int8)
+    return col.vals
+
+
+def expected_order_np(cols, keys, limit=None):
+    """expected_order for the row counts Python's `sorted` is too slow at (fixed-width keys; Utf8 keys drawn from
+    a pool): per key a rank array and a null flag, ordered by one stable np.lexsort. A null ranks above every
+    value (its flag is the more significant word, its rank 0); DESC reverses both words (the complement of an
+    integer reverses its order without overflow). tests/test_sort_cpu.py pins it to expected_order."""
+    n = cols[0].n
+    lex = []  # np.lexsort: the last array is the primary key
+    for j, asc in reversed(keys):
+        null = ~cols[j].valid
+        rank = rank_np(cols[j]).copy()
+        rank[null] = 0
+        lex += [rank if asc else ~rank, null if asc else ~null]
+    order = np.lexsort(lex) if lex else np.arange(n)  # stable: ties keep input order
+    return order if limit is None else order[:limit]
+
+
 def check(out, cols, order):
     assert len(out) == len(cols)
     for a, c in zip(out, cols):
@@ -178,6 +212,24 @@ def column(t, n, rng, nulls, distinct=None):
     vals = take(pool, pick)
     valid = rng.random(n) >= 0.2 if nulls else None
     return Col(t, vals, valid)
+
+
+def entropy(t, n, rng, nulls=True):
+    """n full-entropy 64-bit values (Float64, Int64 or UInt64): uniform random bit patterns, so every digit of the
+    sort word varies. Float64 also gets NaNs of both signs with random payloads and F64_SPECIAL; the integers
+    their extremes -- UInt64's 2^64 - 1 (twice), whose word is a null's."""
+    t = T(t)
+    bits = rng.integers(0, 1 << 64, n, dtype=np.uint64, endpoint=False)
+    if t == T.Float64:
+        bits[::97] |= np.uint64(0x7FF0000000000000)  # exponent all ones, the random sign and mantissa kept: NaNs
+        head = F64_SPECIAL.view(np.uint64)
+    elif t == T.UInt64:
+        head = np.array([2**64 - 1, 2**64 - 1, 0, 2**64 - 2, 2**63, 2**63 - 1, 1], dtype=np.uint64)
+    else:
+        head = np.array([2**63, 2**63 - 1, 2**64 - 1, 0, 1, 2**63 + 1], dtype=np.uint64)  # min, max, -1, 0, 1, min + 1
+    bits[:min(n, len(head))] = head[:n]
+    bits = rng.permutation(bits)
+    return Col(t, bits.view(np_dtype(t)), rng.random(n) >= 0.2 if nulls else None)
 
 
 def payloads(n, rng):

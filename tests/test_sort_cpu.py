@@ -80,3 +80,37 @@ def test_more_than_eight_keys_is_a_program_limit():
         assert e.value.kind == "NotImplemented"
         assert e.value.message.startswith("device program limit: ")
     assert type(ctx.execute(Sort([SortExpr(Column(0), True)] * 8, proj, proj.schema))) is SortRelation
+
+
+# ---- the vectorised restatement the large device tests use is pinned to the comparator one
+def _pin_cases():
+    from test_gpu_sort import ALL_TYPES, Col, column, entropy
+    import numpy as np
+    n = 3000
+    cases = []
+    for t in ALL_TYPES:
+        for asc in (True, False):
+            rng = np.random.default_rng(100 + 2 * int(t) + asc)
+            cases.append(("%s-%s" % (t.name, "asc" if asc else "desc"), [column(t, n, rng, True)], [(0, asc)]))
+    for t in (DataType.Float64, DataType.UInt64, DataType.Int64):
+        for asc in (True, False):
+            rng = np.random.default_rng(200 + 2 * int(t) + asc)
+            cases.append(("entropy-%s-%s" % (t.name, "asc" if asc else "desc"), [entropy(t, n, rng)], [(0, asc)]))
+    rng = np.random.default_rng(300)
+    three = [column(DataType.Utf8, n, rng, True, distinct=5), column(DataType.Float64, n, rng, True, distinct=6),
+             column(DataType.Int8, n, rng, True), Col(DataType.Int32, np.arange(n))]
+    cases.append(("three-keys", three, [(0, False), (1, True), (2, False)]))
+    return cases
+
+
+@pytest.mark.parametrize("name, cols, keys", _pin_cases(), ids=lambda v: v if isinstance(v, str) else "")
+def test_expected_order_np_is_expected_order(name, cols, keys):
+    """expected_order_np (np.lexsort over rank arrays) against expected_order (Python's stable sorted with the
+    comparator) at n = 3,000: every key type in both directions with nulls, the full-entropy 64-bit generators,
+    one three-key order; the whole order and a prefix."""
+    from test_gpu_sort import expected_order, expected_order_np
+    want = expected_order(cols, keys)
+    assert sorted(want) == list(range(cols[0].n))
+    assert list(expected_order_np(cols, keys)) == want
+    assert list(expected_order_np(cols, keys, 17)) == want[:17]
+    assert list(expected_order_np(cols, [])) == list(range(cols[0].n))
