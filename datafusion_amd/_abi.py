@@ -39,6 +39,7 @@ DFMI_FLAG_EXT_UTF8_ORDER = 0x100  # with DFMI_FLAG_EXT_UTF8_COMPARE: Utf8 <, <=,
 DFMI_FLAG_EXT_AGG_MINMAX_ANY = 0x200  # with DFMI_FLAG_EXT_AGGREGATE: MIN / MAX over a Boolean or Utf8 argument
 DFMI_FLAG_EXT_MODULUS = 0x400  # the Modulus operator (%) over the integer and float types
 DFMI_FLAG_EXT_CAST_ANY = 0x800  # with DFMI_FLAG_EXT_CAST: CAST of a Utf8 column (parsed), Boolean <-> numeric
+DFMI_FLAG_EXT_CAST_UTF8 = 0x1000  # with DFMI_FLAG_EXT_CAST: CAST to Utf8 (formatted by dfmi_format_utf8_batches)
 
 # dfmi_agg_fn (AggregateType, expression.rs:33-40)
 DFMI_AGG_MIN = 0
@@ -204,6 +205,7 @@ EXPORTED = [
     "dfmi_shard_agg_finish_grouped",
     "dfmi_agg_state_free",
     "dfmi_sort_batches",
+    "dfmi_format_utf8_batches",
     "dfmi_generate_column",  # include/dfmi_datasource.h
     "dfmi_csv_open",
     "dfmi_csv_next",
@@ -436,5 +438,8 @@ def lib() -> C.CDLL:
     L.dfmi_sort_batches.argtypes = [C.c_void_p, P(dfmi_batch), C.c_int32, P(C.c_int32), P(C.c_int32), C.c_int32,
                                     C.c_int64, P(dfmi_out_column), C.c_uint32, P(dfmi_error)]
     L.dfmi_sort_batches.restype = C.c_int32
+    L.dfmi_format_utf8_batches.argtypes = [C.c_void_p, P(dfmi_column), P(C.c_int64), C.c_int32, P(dfmi_out_column),
+                                           P(C.c_int64), C.c_uint32, P(dfmi_error)]
+    L.dfmi_format_utf8_batches.restype = C.c_int32
     _LIB = L
     return L

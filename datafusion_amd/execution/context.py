@@ -184,7 +184,7 @@ class ExecutionContext:
         if isinstance(plan, Selection):
             input_rel = self.execute(plan.input)
             input_schema = input_rel.schema()
-            rt = compile_scalar_expr(self, plan.expr, input_schema, self.flags)
+            rt = compile_scalar_expr(self, plan.expr, input_schema, self.flags, allow_format=False)
             return FilterRelation(input_rel, rt, input_schema, self.device, self.flags, self.coalesce)
         if isinstance(plan, Projection):
             input_rel = self.execute(plan.input)
@@ -226,14 +226,14 @@ class ExecutionContext:
         inp, pred = plan.input, None
         if isinstance(inp, Selection):
             source = self.execute(inp.input)
-            pred = compile_scalar_expr(self, inp.expr, source.schema(), self.flags)
+            pred = compile_scalar_expr(self, inp.expr, source.schema(), self.flags, allow_format=False)
         else:
             source = self.execute(inp)
         input_schema = source.schema()
         keys = []
         fields = []
         for g in plan.group_expr:  # GROUP BY extension: the key columns first (sqlplanner.rs:106-109)
-            k = compile_scalar_expr(self, g, input_schema, self.flags)
+            k = compile_scalar_expr(self, g, input_schema, self.flags, allow_format=False)
             keys.append(k)
             fields.append(Field(k.get_name(), DataType(k.get_type()), True))
         aggs = [compile_expr(self, e, input_schema, self.flags) for e in plan.aggr_expr]

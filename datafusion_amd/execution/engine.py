@@ -19,6 +19,11 @@ from .error import ExecutionError
 
 _ENGINES = {}
 
+# bytes per row that always suffice for CAST to Utf8 (include/dfmi.h, dfmi_format_utf8_batches)
+_FORMAT_WORST = {DataType.Boolean: 5, DataType.Int8: 4, DataType.Int16: 6, DataType.Int32: 11, DataType.Int64: 20,
+                 DataType.UInt8: 3, DataType.UInt16: 5, DataType.UInt32: 10, DataType.UInt64: 20,
+                 DataType.Float32: 48, DataType.Float64: 327}
+
 
 def engine(device=None) -> "DeviceEngine":
     if device is None:
@@ -28,6 +33,13 @@ def engine(device=None) -> "DeviceEngine":
     if idx not in _ENGINES:
         _ENGINES[idx] = DeviceEngine(idx)
     return _ENGINES[idx]
+
+
+def _no_format(projections, what: str) -> None:
+    """CAST(e AS Utf8) projections (the "format" mark) are formatted on the device after the fused pass, by
+    filter_project / filter_project_batches only: every other form would hand back the child's column."""
+    if any(getattr(p, "format", False) for p in projections or []):
+        raise ExecutionError("NotImplemented", "CAST to Utf8 in %s (device batches only)" % what)
 
 
 def column_struct(a: Array) -> _abi.dfmi_column:
@@ -113,6 +125,8 @@ class DeviceEngine:
         n = batch.num_rows()
         cols = batch.columns
         projections = list(projections or [])
+        if comm is not None:
+            _no_format(projections, "a sharded pass")
         carr = (_abi.dfmi_column * max(1, len(cols)))()
         for i, a in enumerate(cols):
             carr[i] = column_struct(a)
@@ -141,14 +155,18 @@ class DeviceEngine:
             L.dfmi_last_error_order(self.ctx, C.byref(key))
             e.order_key = key.value  # evaluation-order position (sharded callers pick the first)
             raise e
-        return self._results(out_types, [outs[o] for o in range(len(out_types))], keeps, cols)
+        result = self._results(out_types, [outs[o] for o in range(len(out_types))], keeps, cols)
+        self._format_marked(projections, [result], flags)  # (never with a comm: refused above)
+        return result
 
     def _prepare_outputs(self, predicate, projections, cols, n):
         """Output types, dfmi_out_column structs (worst-case buffers for n
         rows) and the tensors behind them, for one batch."""
         if projections:
-            out_types = [p.get_type() for p in projections]
-            src_cols = [p.expr.index if isinstance(p.expr, Column) else None for p in projections]
+            # (a projection with the "format" mark, CAST(e AS Utf8): the fused pass runs its child)
+            fused = [p.child if getattr(p, "format", False) else p for p in projections]
+            out_types = [p.get_type() for p in fused]
+            src_cols = [p.expr.index if isinstance(p.expr, Column) else None for p in fused]
         else:
             out_types = [c.data_type for c in cols]
             src_cols = list(range(len(cols)))
@@ -237,7 +255,72 @@ class DeviceEngine:
         for i in range(done):
             results.append(self._results(per[i][0], [outs[i * nout + o] for o in range(nout)], per[i][2],
                                          batches[i].columns))
+        self._format_marked(projections, results, flags)
         return results, error
+
+    def _format_marked(self, projections, results, flags: int) -> None:
+        """CAST(e AS Utf8) projections (the "format" mark): their fixed-width
+        outputs in every column list of `results` -- all batches of the call --
+        become Utf8 Arrays through ONE dfmi_format_utf8_batches."""
+        marked = [o for o, p in enumerate(projections) if getattr(p, "format", False)]
+        if not marked or not results:
+            return
+        done = self.format_utf8([cols[o] for cols in results for o in marked], flags)
+        it = iter(done)
+        for cols in results:
+            for o in marked:
+                cols[o] = next(it)
+
+    def format_utf8(self, arrays: Sequence[Array], flags: int) -> List[Array]:
+        """Device Boolean / numeric Arrays as Utf8 Arrays (validity and null
+        count kept, a null row's slot empty): dfmi_format_utf8_batches, one
+        call for all of them. Integer and Boolean outputs are allocated at the
+        type's worst case; floats are measured first (one more call over the
+        float columns with no data buffer) and allocated exactly."""
+        self.drain()
+        L = _abi.lib()
+        arrays = list(arrays)
+        n = len(arrays)
+        if n == 0:
+            return []
+        carr = (_abi.dfmi_column * n)(*[column_struct(a) for a in arrays])
+        rows = (C.c_int64 * n)(*[a.length for a in arrays])
+        L.dfmi_context_set_stream(self.ctx, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+
+        def call(cols, nrows, outs, count):
+            lens = (C.c_int64 * count)()
+            err = _abi.dfmi_error()
+            rc = L.dfmi_format_utf8_batches(self.ctx, cols, nrows, count, outs, lens, flags, C.byref(err))
+            if rc != _abi.DFMI_OK:
+                raise ExecutionError.from_status(rc, err.message.decode("utf-8", errors="replace"))
+            return lens
+
+        keeps = []
+        outs = (_abi.dfmi_out_column * n)()
+        for i, a in enumerate(arrays):
+            k = {"offsets": torch.empty(max(16, a.length + 1 + 15), dtype=torch.int32, device=self.device)}
+            if a.validity is not None and a.null_count:
+                k["validity"] = empty_bytes((a.length + 63) // 64 * 8, self.device)
+                outs[i].validity = k["validity"].data_ptr()
+            outs[i].offsets = k["offsets"].data_ptr()
+            keeps.append(k)
+        floats = [i for i, a in enumerate(arrays) if a.data_type in (DataType.Float32, DataType.Float64)]
+        need = {}
+        if floats:
+            m = len(floats)
+            fcols = (_abi.dfmi_column * m)(*[carr[i] for i in floats])
+            frows = (C.c_int64 * m)(*[rows[i] for i in floats])
+            fouts = (_abi.dfmi_out_column * m)(*[outs[i] for i in floats])  # (data NULL: measure only)
+            lens = call(fcols, frows, fouts, m)
+            need = {i: lens[j] for j, i in enumerate(floats)}
+        for i, a in enumerate(arrays):
+            cap = need[i] if i in need else _FORMAT_WORST[a.data_type] * a.length
+            keeps[i]["data"] = empty_bytes(max(cap, 8), self.device)
+            outs[i].data = keeps[i]["data"].data_ptr()
+            outs[i].data_capacity = cap
+        call(carr, rows, outs, n)
+        return [Array(DataType.Utf8, outs[i].length, keeps[i]["data"], keeps[i].get("validity"), keeps[i]["offsets"],
+                      outs[i].null_count) for i in range(n)]
 
     def filter_project_host(self, predicate, projections: Optional[Sequence], batch: RecordBatch,
                             flags: int = 0) -> List[Array]:
@@ -250,6 +333,7 @@ class DeviceEngine:
         if any(c.values.device.type != "cpu" for c in cols):
             raise ValueError("filter_project_host takes a host batch")
         projections = list(projections or [])
+        _no_format(projections, "filter_project_host")
         carr = (_abi.dfmi_column * max(1, len(cols)))()
         for i, a in enumerate(cols):
             carr[i] = column_struct(a)
@@ -320,6 +404,7 @@ class DeviceEngine:
 
     def _host_batches_prepare(self, predicate, projections, batches, flags):
         projections = list(projections or [])
+        _no_format(projections, "the host batch forms")
         nb = len(batches)
         ncols = batches[0].num_columns() if nb else 0
         nout = len(projections) if projections else ncols

@@ -10,7 +10,7 @@ import ctypes as C
 
 from .. import _abi
 from ..arrow import Schema
-from ..logicalplan import AggregateFunction, DataType, Expr
+from ..logicalplan import AggregateFunction, Cast, Column, DataType, Expr, Literal
 from .error import ExecutionError
 
 
@@ -50,11 +50,57 @@ def schema_struct(schema: Schema):
     return _abi.make_schema([(f.name, f.data_type, f.nullable) for f in schema.fields])
 
 
-def compile_scalar_expr(ctx, expr: Expr, input_schema: Schema, flags: int = None) -> RuntimeExpr:
+class FormatExpr:
+    """CAST(e AS Utf8) as the root of a projection (DFMI_FLAG_EXT_CAST with
+    DFMI_FLAG_EXT_CAST_UTF8): the fused pass runs the compiled CHILD -- `handle`
+    is its program, `child` its RuntimeExpr -- into a fixed-width column, which
+    the engine then formats (dfmi_format_utf8_batches). `format` is the mark the
+    engine and ProjectRelation look for."""
+
+    format = True
+
+    def __init__(self, expr: Cast, child: RuntimeExpr):
+        self.expr = expr
+        self.child = child
+        self.flags = child.flags
+        self.name = repr(expr)  # "CAST(#0 AS Utf8)": expr_debug's text
+        self.t = DataType.Utf8
+        self.input_schema = child.input_schema
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self.child.handle
+
+    def get_name(self) -> str:
+        return self.name
+
+    def get_type(self) -> DataType:
+        return self.t
+
+
+_CAST_UTF8 = _abi.DFMI_FLAG_EXT_CAST | _abi.DFMI_FLAG_EXT_CAST_UTF8
+_FORMATTED = (DataType.Boolean, DataType.Int8, DataType.Int16, DataType.Int32, DataType.Int64, DataType.UInt8,
+              DataType.UInt16, DataType.UInt32, DataType.UInt64, DataType.Float32, DataType.Float64)
+
+
+def compile_scalar_expr(ctx, expr: Expr, input_schema: Schema, flags: int = None, allow_format: bool = True):
     """expression.rs:244 — raises ExecutionError exactly where the reference's
-    compile_scalar_expr returns Err."""
+    compile_scalar_expr returns Err. Under DFMI_FLAG_EXT_CAST_UTF8 a root
+    CAST(e AS Utf8) gives a FormatExpr over the compiled child (a Utf8 column
+    child: the column itself under the cast's name); allow_format=False -- a
+    predicate, an aggregate argument, a GROUP BY key -- leaves such a cast to
+    the library, which rejects it as before."""
     if flags is None:
         flags = getattr(ctx, "flags", 0) if ctx is not None else 0
+    if (allow_format and (flags & _CAST_UTF8) == _CAST_UTF8 and isinstance(expr, Cast)
+            and expr.data_type == DataType.Utf8 and not isinstance(expr.expr, Literal)):
+        child = compile_scalar_expr(ctx, expr.expr, input_schema, flags, allow_format=False)
+        if child.get_type() == DataType.Utf8 and isinstance(expr.expr, Column):
+            child.name = repr(expr)
+            return child
+        if child.get_type() in _FORMATTED:
+            return FormatExpr(expr, child)
+        # (anything else: the library's own error below)
     nodes = _abi.PostfixNodes(expr.to_postfix())
     sch, keep = schema_struct(input_schema)
     out = C.c_void_p()
@@ -110,7 +156,7 @@ def compile_expr(ctx, expr: Expr, input_schema: Schema, flags: int = None):
     if len(expr.args) != 1:  # assert_eq!(1, args.len())
         raise ExecutionError("panic", "assertion failed: `(left == right)`\n  left: `1`,\n right: `%d`"
                              % len(expr.args))
-    arg = compile_scalar_expr(ctx, expr.args[0], input_schema, flags)
+    arg = compile_scalar_expr(ctx, expr.args[0], input_schema, flags, allow_format=False)
     out = C.c_void_p()
     err = _abi.dfmi_error()
     rc = _abi.lib().dfmi_compile_aggregate(expr.name.encode("utf-8"), arg.handle, int(expr.return_type), flags,

@@ -33,6 +33,11 @@ class ProjectRelation(Relation):
             if isinstance(input, FilterRelation):
                 flags |= input.flags
         self.flags = flags
+        # CAST(e AS Utf8) projections (DFMI_FLAG_EXT_CAST_UTF8) are formatted on the
+        # device after the fused pass: such a list takes the device forms for
+        # every batch -- a host batch (CSV source) is uploaded first and its
+        # results are device arrays, unlike the host entry points' host results
+        self._format = any(getattr(e, "format", False) for e in self.expr)
 
     def _source_and_predicate(self):
         if isinstance(self.input, FilterRelation):
@@ -60,7 +65,7 @@ class ProjectRelation(Relation):
     def run_batch(self, batch: RecordBatch):
         _, pred = self._source_and_predicate()
         eng = engine(self.device)
-        if is_host_batch(batch):
+        if is_host_batch(batch) and not self._format:
             # a host batch (e.g. a CSV source's pinned buffers): the pipelined
             # host entry point, host results -- what a Rust caller gets
             return eng.filter_project_host(pred, self.expr, batch, self.flags)
@@ -72,6 +77,10 @@ class ProjectRelation(Relation):
             return co.next()
         source, pred = self._source_and_predicate()
         if self.coalesce > 1:  # up to `coalesce` input batches per device launch
+            if self._co is None and self._format:
+                many = lambda bs: engine(self.device).filter_project_batches(pred, self.expr, bs, self.flags)
+                self._co = Coalescer(self.coalesce, source, self.run_batch, many, self._wrap, many,
+                                     wrap_many=self._wrap_many)
             if self._co is None:
                 self._co = Coalescer(self.coalesce, source, self.run_batch,
                                      lambda bs: engine(self.device).filter_project_batches(pred, self.expr, bs,

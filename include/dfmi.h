@@ -407,6 +407,56 @@ typedef struct dfmi_expr_node {
  *             batch form; sliced arrays.
  * One flag bit, no struct change, no new entry point: DFMI_ABI_VERSION stays 4. */
 
+#define DFMI_FLAG_EXT_CAST_UTF8    0x1000u
+/* CAST to Utf8: numbers and Booleans formatted on the device. Effective only
+ * together with DFMI_FLAG_EXT_CAST; without both flags everything compiles and
+ * fails exactly as before (dfmi_compile_scalar_expr answers
+ * NotImplemented("CAST from Int64 to Utf8") and so on). Build-defined, parity
+ * unpinned: the reference executes no CAST of a column. The convention is
+ * "what Rust on x86-64 prints" (to_string / Display), so the native CSV reader
+ * (dfmi_csv_*) and CAST(s AS T) under DFMI_FLAG_EXT_CAST_ANY read every output
+ * back to the value it came from.
+ *   forms:    CAST(e AS Utf8) as the ROOT of a projection expression (also a
+ *             non-Column ORDER BY key, which is evaluated as a projection),
+ *             e of type Boolean, Int8..Int64, UInt8..UInt64, Float32 or
+ *             Float64, or a Utf8 COLUMN (identity: the column itself). Name
+ *             "CAST(#i AS Utf8)", type Utf8. The fused pass
+ *             (dfmi_filter_project*) is not changed: a binding compiles and
+ *             runs the cast's CHILD as an ordinary fixed-width projection and
+ *             hands the resulting device column to dfmi_format_utf8_batches
+ *             below. dfmi_compile_scalar_expr itself keeps its error for every
+ *             cast to Utf8, so one anywhere else -- under a comparison, as an
+ *             aggregate argument, as a GROUP BY key, with a Utf8 literal child
+ *             -- fails with today's text;
+ *   nulls:    a null stays a null: an empty slot, the validity copied from the
+ *             child's. Nothing raises at run time but the one program limit
+ *             below. After a Selection the child column is all-valid and a null
+ *             slot is formatted by its raw bits (the rule of Utf8 `=`);
+ *   Boolean:  "true" / "false";
+ *   integers: ASCII digits without leading zeros, a leading '-' for negative
+ *             values: i64::MIN is "-9223372036854775808" (20 bytes), u64::MAX
+ *             "18446744073709551615" (20 bytes);
+ *   floats:   never exponent notation. The digits are the SHORTEST decimal
+ *             digit string that reads back to the same float in the value's
+ *             own width (Float32 is not widened: 0.1f32 is "0.1"); of several
+ *             shortest strings the one closest to the value, a tie between two
+ *             going to the even last digit; an end of the rounding interval
+ *             counts as inside when the significand is even (it reads back by
+ *             ties-to-even) -- what Rust's Grisu with its Dragon fallback, Ryu,
+ *             CPython's repr and std::to_chars produce. The digits are laid out
+ *             positionally: "1", "0.1", "1000000000000000000000" for 1e21,
+ *             "100000000000000000000000" for 1e23 (the shortest digits, then
+ *             zeros: not the float's exact integer value), "0.000..005" for
+ *             5e-324. An integral value has no ".0". -0.0 is "-0" (current Rust
+ *             prints it so, and the sign survives the round trip). Infinities
+ *             are "inf" / "-inf"; every NaN is "NaN", sign and payload dropped
+ *             (it reads back as the positive quiet NaN). The longest Float64
+ *             string is 327 bytes ("-0." 323 zeros "5" for -5e-324), the
+ *             longest Float32 string 48 bytes (-1e-45);
+ *   limit:    a column of 2^31 or more output bytes is DFMI_ERR_NOT_IMPLEMENTED
+ *             "device program limit: CAST to Utf8 output of 2^31 or more bytes".
+ * One flag bit, one new entry point, no struct change: DFMI_ABI_VERSION stays 4. */
+
 /* Signature of a built-in scalar function, for a binding's
  * SchemaProvider::get_function_meta (sqlplanner.rs:330-350 casts each
  * argument to arg_types[i]). Returns 0 and fills *num_args, *return_type and
@@ -867,6 +917,43 @@ int32_t dfmi_sort_batches(dfmi_context* ctx, const dfmi_batch* inputs, int32_t n
                           const int32_t* key_columns, const int32_t* key_asc, int32_t num_keys,
                           int64_t limit /* < 0: none */, dfmi_out_column* outputs,
                           uint32_t flags, dfmi_error* err);
+
+/* ---------------------------------------------------------------------------
+ * CAST to Utf8 (DFMI_FLAG_EXT_CAST with DFMI_FLAG_EXT_CAST_UTF8; the values'
+ * text is specified at the flag). Formats `num_columns` device columns, each
+ * of Boolean or a fixed-width numeric type, with num_rows[i] = columns[i].length
+ * rows (0 allowed, sliced columns through dfmi_column.offset), into arrow Utf8
+ * arrays -- all the batches of a coalesced pull in ONE call: the kernels run
+ * once over every column together. For each column the library writes
+ *   outputs[i].offsets[0..n]  int32, starting at 0 (caller: n + 1 words);
+ *   outputs[i].validity       the input's validity, bits past n in the last
+ *                             64-bit word zero, when the input has nulls
+ *                             (validity != NULL and null_count > 0; caller:
+ *                             ceil(n / 64) * 8 bytes, 8-byte aligned); a null
+ *                             row's slot is empty;
+ *   outputs[i].data           the bytes, data_capacity of them at the most;
+ *   data_lengths[i]           the bytes the column needs -- always, also when
+ *                             the call fails on a capacity or on the limit;
+ * and fills type = Utf8, passthrough_column = -1, length, null_count and
+ * data_length. Measure mode: with outputs[i].data == NULL the column's offsets
+ * and data_lengths[i] are written and no byte is. A Float64 caller measures,
+ * allocates exactly and calls again; for the other types the worst case is
+ * small enough to allocate at once. Bytes per row that always suffice:
+ *     UInt8 3   UInt16 5   UInt32 10   UInt64 20   Boolean 5
+ *     Int8  4   Int16  6   Int32  11   Int64  20   Float32 48   Float64 327
+ * Errors: data_capacity below the need is DFMI_ERR_CAPACITY (data_lengths set,
+ * no byte of any column written); a column of 2^31 or more output bytes, or
+ * 2^31 or more rows in the call, DFMI_ERR_NOT_IMPLEMENTED "device program
+ * limit: ..."; a call without both flags DFMI_ERR_NOT_IMPLEMENTED; a Utf8
+ * input, another type, a length that differs from num_rows[i] or a NULL buffer
+ * DFMI_ERR_INVALID_ARGUMENT. Synchronous. The context keeps the call's scratch
+ * (8 bytes per input row, rounded up to 256 rows per column, plus the scan's)
+ * for later calls and frees it in dfmi_context_destroy: about 0.8 GB after a
+ * call over 1e8 rows.
+ * ------------------------------------------------------------------------- */
+int32_t dfmi_format_utf8_batches(dfmi_context* ctx, const dfmi_column* columns, const int64_t* num_rows,
+                                 int32_t num_columns, dfmi_out_column* outputs, int64_t* data_lengths,
+                                 uint32_t flags, dfmi_error* err);
 
 /* ---------------------------------------------------------------------------
  * Multi-GPU. The reference is single-threaded (context.rs:33);
