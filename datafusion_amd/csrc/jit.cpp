@@ -142,6 +142,18 @@ struct Gen {
         X.args_lits[X.n_lits] = b;
         return X.n_lits++;
     }
+    // ... and one slot per node however often it is emitted: the aggregate
+    // kernel's sub-tile form emits every argument twice (the list pass and the
+    // lane-masked pass of a wave whose list overflowed), and a second set of
+    // slots would halve the 32 a query may use in that form only
+    // (`which`: 0 the node's literal, 1 a literal divisor's reciprocal)
+    std::map<std::tuple<const dfmi_program*, int, int>, int> lit_slots;
+    int lit_at(const dfmi_program* p, int node, int which, uint64_t b) {
+        const auto key = std::make_tuple(p, node, which);
+        const auto it = lit_slots.find(key);
+        if (it != lit_slots.end()) return it->second;
+        return lit_slots[key] = lit(b);
+    }
     int strlit(const std::string& s) {
         if (X.n_str >= 8 || X.str_bytes + (int)s.size() > 256)
             throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "query compiler: string literals too long"};
@@ -239,7 +251,7 @@ struct Gen {
             if (n.type == DFMI_TYPE_UTF8) return Val{"", "true"};
             if (!type_width(n.type))
                 throw Fail{DFMI_ERR_NOT_IMPLEMENTED, std::string("device path: ") + type_debug(n.type) + " literal"};
-            return Val{lit_value(n.type, lit(n.bits)), "true"};
+            return Val{lit_value(n.type, lit_at(p, i, 0, n.bits)), "true"};
         }
         if (n.kind == IR_ISNULL) {  // extension: the operand's validity, never null
             const Val a = emit(p, n.l, ord_base, act);
@@ -405,7 +417,7 @@ struct Gen {
                 o << "    " << ct << " " << v << " = dfmi::fn_mod<" << ct << ">(" << a.v << ", " << b.v << ");\n";
             else if (R.kind == IR_LIT && g_rem_literal)  // the reciprocal in a literal slot of its own
                 o << "    " << ct << " " << v << " = dfmi::irem_lit<" << ct << ">(" << a.v << ", " << b.v << ", A.lits["
-                  << lit(rem_reciprocal(type_width(ty), is_signed_int(ty), R.bits)) << "]);\n";
+                  << lit_at(p, i, 1, rem_reciprocal(type_width(ty), is_signed_int(ty), R.bits)) << "]);\n";
             else
                 o << "    " << ct << " " << v << " = dfmi::irem<" << ct << ">(" << a.v << ", " << b.v << ");\n";
         } else if (f) {
