@@ -1,7 +1,7 @@
 // Aggregate extension: the coalesced entry points. Many small batches (the
 // reference streams 1024-row batches through Relation::next) accumulated into
 // one dfmi_agg_state by one call: one batch table H2D, one launch of the
-// batched form of the aggregate kernel (jit.cpp emit_batched_prologue: a
+// batched form of the aggregate kernel (jit_kernels.cpp emit_batched_prologue: a
 // block finds its batch through Args::tile_batch and takes its rows, columns
 // and error word from its row of Args::batch_ptrs), one D2H of the per-batch
 // headers, one synchronisation -- instead of all of that once per batch.

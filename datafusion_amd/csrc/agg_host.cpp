@@ -300,7 +300,7 @@ KeyPart fixed_part(int kt, uint64_t bits) {
 // ---- per-row rules on the host (the host merge: diagnostics A/B, and the
 // rows of a batch whose key shares its 63-bit hash with another key's).
 // One value (row i, non-null) of aggregate `a` into p -- the per-row rules
-// of the aggregate kernels (jit.cpp generate_agg / generate_agg_grouped,
+// of the aggregate kernels (jit_kernels.cpp generate_agg / generate_agg_grouped,
 // jit_skeleton.hip agg_key / agg_sum_flags / fsum_add), restated on the host.
 template <typename T>
 uint64_t host_agg_key(T v) {

@@ -6,7 +6,7 @@
 // AggregateFunction with compile_expr (expression.rs:81-116) and then stops:
 // ExecutionContext::execute has no Aggregate arm (context.rs:161
 // `unimplemented!()`). Here every input batch is one launch of a
-// query-compiled kernel (jit.cpp generate_agg): predicate, argument and
+// query-compiled kernel (jit_kernels.cpp generate_agg): predicate, argument and
 // reduction fused, partials accumulated in device memory across batches; the
 // host merges the accumulator copies exactly and rounds once at the end.
 //
@@ -127,7 +127,7 @@ void build_agg_plan(const dfmi_agg_state* st, const dfmi_program* pred, const df
     // a predicate that selected < 4% of the rows the last time this state
     // ran the query (dfmi_aggregate_batch keeps the kernel's count): M
     // sub-tiles per block, the arguments loaded by one lane per selected row
-    // (jit.cpp generate_agg; numeric, non-Boolean arguments)
+    // (jit_kernels.cpp generate_agg; numeric, non-Boolean arguments)
     bool can_sub = pred && !st->grouped && X.utf8_cols.empty();
     for (int s : X.proj_slots) can_sub = can_sub && X.col_type(X.num_cols[s]) != DFMI_TYPE_BOOLEAN;
     for (int s : X.pred_slots) can_sub = can_sub && X.col_type(X.num_cols[s]) != DFMI_TYPE_BOOLEAN;

@@ -1,7 +1,7 @@
 // What a column's buffers weigh and which columns a program reads: the host
 // arithmetic shared by every path that stages host columns (host_plan.cpp,
 // host_batches.cpp, agg_batches.cpp) or walks them (csv_reader.cpp,
-// slice.cpp, sort.cpp, jit.cpp). Host only: no HIP.
+// slice.cpp, sort.cpp, jit_*.cpp). Host only: no HIP.
 #pragma once
 #include <algorithm>
 #include <cstddef>

@@ -4,7 +4,7 @@
 // static errors in the reference's evaluation order, output metadata, which
 // input columns the kernel loads (predicate columns for every row,
 // projection-only columns only where selected); gets the query kernel from
-// the query compiler (jit.cpp), launches it, and maps device error words back
+// the query compiler (jit.h), launches it, and maps device error words back
 // to the reference's errors (FilterRelation::next filter.rs:46-72, filter()
 // filter.rs:80-111, ProjectRelation::next projection.rs:45-66).
 #include <hip/hip_runtime.h>
@@ -72,7 +72,7 @@ constexpr bool kRingDefault = false;
 // sub-tile kernel: M sub-tiles of BLOCK * K rows share one scan + look-back
 // (one look-back per 16,384 rows instead of per 4,096), the predicate pass
 // keeps only selection ballots, and the output pass reloads just the columns
-// the outputs read, for the selected rows (jit.cpp "M sub-tiles"). Chosen
+// the outputs read, for the selected rows (jit_kernels.cpp "M sub-tiles"). Chosen
 // from the selectivity the same query shape had on its previous large batch
 // on this context (below kLowSel); the first call, and any call after a
 // batch selected more, runs the one-tile kernel, which keeps every loaded

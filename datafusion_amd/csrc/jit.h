@@ -1,9 +1,10 @@
-// Query compiler interface (host side of jit.cpp).
+// Query compiler interface (jit_expr.cpp, jit_kernels.cpp, jit_cache.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -47,11 +48,14 @@ struct Plan {
     int gslots = 0;
 };
 
-// Slot tables + literal pools of one launch.
-struct Launch {
+// The knobs that shape the generated code, and only those: get_kernel's
+// shape key (jit_cache.cpp) is this struct's bytes, so a knob that changes the
+// source text belongs here and nowhere else -- in Launch proper it would be
+// missing from the key and a cache hit would launch another shape's kernel.
+// ints only (no padding: the static_assert below).
+struct TileShape {
     int K = 8, BLOCK = 512;
     int waves_per_eu = 0;  // >0: occupancy hint to the register allocator
-    bool waves_soft = false;  // ... dropped (recompiled without) when meeting it spills
     // look-back: R windows of 64 status words per round trip, s_sleep(sleep)
     // between polls, one status word per `spread` words (16 = one per 128-byte
     // line: polling blocks then do not contend on shared lines)
@@ -117,27 +121,41 @@ struct Launch {
     int dbuf = 0;      // gather 1 / 4 / 5: the arena's halves double-buffer the staging (ARENA >= 256)
     int image = 129;   // gather 4: LDS image per wave, 16-byte chunks (a longer slice output copies per lane)
     int st16 = 0;      // gather 4: the image 16-byte aligned, stored with 16-byte stores (edge words apart)
-    int prestage = 0;
-    int gather_phases = 0;  // diagnostics: per-phase cycle counters in utf8_gather (DFMI_DEBUG_MODE bit 5)  // gather 1 / 4: the first staging round is issued before the look-back
+    int prestage = 0;       // gather 1 / 4: the first staging round is issued before the look-back
+    int gather_phases = 0;  // diagnostics: per-phase cycle counters in utf8_gather (DFMI_DEBUG_MODE bit 5)
     // cache policy of the column streams: bit0 nontemporal loads, bit1 nontemporal stores
     int nt = 0;
+    // coalesced batches (dfmi_filter_project_batches): blocks map to batches
+    // through Args::tile_batch, and each batch's sizes and buffers come from
+    // its row of Args::batch_ptrs (layout: batch_slot_* below)
+    int batched = 0;
+};
+static_assert(std::has_unique_object_representations_v<TileShape>, "TileShape is hashed as bytes");
+
+// The literal tables of one generated kernel, as bind_literals hands them to
+// the kernel's Args.
+struct LitPool {
+    uint64_t bits[32] = {};  // one slot per literal node (raw bits)
+    int n_lits = 0;
+    int str_off[8] = {}, str_len[8] = {};
+    char str[256] = {};
+    int n_str = 0, str_bytes = 0;
+};
+
+// Tile shape, slot tables + literal pools of one launch.
+struct Launch : TileShape {
+    // the waves_per_eu hint is dropped (the shape compiled again without it)
+    // when meeting it spills: chooses whether to recompile, not the text
+    bool waves_soft = false;
     const dfmi_batch* in = nullptr;
     std::vector<int> num_cols;   // arg slot -> input column (numeric and Boolean)
     std::vector<int> pred_slots; // slots the predicate reads (loaded for every row)
     std::vector<int> proj_slots; // slots only projections read (loaded where selected)
     std::vector<int> utf8_cols;  // utf8 slot -> input column
     std::vector<std::pair<int, int>> utf8_outs;  // (output index, utf8 slot)
-    uint64_t args_lits[32] = {};
-    int n_lits = 0;
-    int str_off[8] = {}, str_len[8] = {};
-    char str[256] = {};
-    int n_str = 0, str_bytes = 0;
+    LitPool lits;
     std::string kname;  // generated kernel's name (dfmi_<kind>_<hash>)
     std::shared_ptr<const void> module;  // keeps the kernel's code object loaded (get_kernel)
-    // coalesced batches (dfmi_filter_project_batches): blocks map to batches
-    // through Args::tile_batch, and each batch's sizes and buffers come from
-    // its row of Args::batch_ptrs (layout: batch_slot_* below)
-    bool batched = false;
 
     int col_type(int col) const { return in->columns[col].type; }
     bool col_nullable(int col) const {

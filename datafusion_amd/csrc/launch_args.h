@@ -55,10 +55,11 @@ inline hipFunction_t query_kernel(dfmi_context* ctx, const jit::Plan& plan, jit:
 
 // The literal slots of the kernel X names (they differ between kernels).
 inline void bind_literals(Args& A, const jit::Launch& X) {
-    memcpy(A.lits, X.args_lits, sizeof A.lits);
-    memcpy(A.str_off, X.str_off, sizeof A.str_off);
-    memcpy(A.str_len, X.str_len, sizeof A.str_len);
-    memcpy(A.str, X.str, sizeof A.str);
+    const jit::LitPool& L = X.lits;
+    memcpy(A.lits, L.bits, sizeof A.lits);
+    memcpy(A.str_off, L.str_off, sizeof A.str_off);
+    memcpy(A.str_len, L.str_len, sizeof A.str_len);
+    memcpy(A.str, L.str, sizeof A.str);
 }
 
 // The lease's header words and what the launch clears for the next one

@@ -353,7 +353,7 @@ def split_table(tab, sizes):
 
 
 # -------------------------------------------------------------- the generator
-LIT_SLOTS, STR_SLOTS, STR_BYTES, MAX_OUTPUTS = 32, 8, 256, 16  # jit.cpp: Gen::lit, Gen::strlit; dfmi.h: 16 outputs
+LIT_SLOTS, STR_SLOTS, STR_BYTES, MAX_OUTPUTS = 32, 8, 256, 16  # jit_expr.cpp: Gen::lit, Gen::strlit; dfmi.h: 16 outputs
 
 
 class Gen:

@@ -1,4 +1,4 @@
-"""The aggregate kernel's sub-tile form (jit.cpp generate_agg, Launch::M > 1):
+"""The aggregate kernel's sub-tile form (jit_kernels.cpp generate_agg, Launch::M > 1):
 M sub-tiles per block, the predicate passes keep the wave's ballots and a list
 of its selected rows, then one lane per selected row loads the arguments and
 accumulates -- or, when a wave selected more rows than its list holds, the

@@ -1,4 +1,4 @@
-"""The hipRTC module cache is bounded (jit.cpp `compile`, least recently used
+"""The hipRTC module cache is bounded (jit_cache.cpp `compile`, least recently used
 evicted): with the bound at 2 modules, four query shapes in turn leave at most
 2 loaded, and a shape whose module was evicted is compiled again and still
 returns the oracle's result (its shape-cache entry went stale with it)."""

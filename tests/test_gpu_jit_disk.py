@@ -1,4 +1,4 @@
-"""The on-disk code-object cache (csrc/jit.cpp, DFMI_JIT_CACHE_DIR): a query
+"""The on-disk code-object cache (csrc/jit_cache.cpp, DFMI_JIT_CACHE_DIR): a query
 shape compiled by one process is loaded, not compiled, by the next -- the
 reference's compile_scalar_expr is a cheap closure build per query
 (context.rs:131,152-155), so a fresh process must not pay ~190 ms of hipRTC

@@ -1,5 +1,5 @@
 """GPU parity of the low-selectivity form of numeric predicates (exec.cpp
-kLowSel, jit.cpp "M sub-tiles"): M sub-tiles share one scan + look-back, the
+kLowSel, jit_kernels.cpp "M sub-tiles"): M sub-tiles share one scan + look-back, the
 predicate pass keeps only selection ballots, and the output pass reloads the
 columns the outputs read for the selected rows -- one lane per row while a
 wave holds at most 256 of them, else a dense pass per slice group. Forced

@@ -11,7 +11,7 @@ lane-masked 8-byte loads: FETCH_SIZE x 2 = 128 B x the 128-byte lines that
 hold a loaded row, exactly; a line loaded again after it left the L2 counts
 again (Infinity-Cache hits included), so these are memory-side request
 bytes, an upper bound on HBM bytes. Query kernels are named per shape
-(dfmi_<filter|project|agg>_<hash>, jit.cpp), so every bench line's kernel has
+(dfmi_<filter|project|agg>_<hash>, jit_kernels.cpp), so every bench line's kernel has
 its own row. Writes <dir>/traffic.json, which bench.py reads to report
 roofline.traffic next to the formula bytes.
 
