@@ -40,6 +40,7 @@ DFMI_FLAG_EXT_AGG_MINMAX_ANY = 0x200  # with DFMI_FLAG_EXT_AGGREGATE: MIN / MAX 
 DFMI_FLAG_EXT_MODULUS = 0x400  # the Modulus operator (%) over the integer and float types
 DFMI_FLAG_EXT_CAST_ANY = 0x800  # with DFMI_FLAG_EXT_CAST: CAST of a Utf8 column (parsed), Boolean <-> numeric
 DFMI_FLAG_EXT_CAST_UTF8 = 0x1000  # with DFMI_FLAG_EXT_CAST: CAST to Utf8 (formatted by dfmi_format_utf8_batches)
+DFMI_FLAG_EXT_CSV_WRITE = 0x2000  # PhysicalPlan::Write: result batches as CSV (dfmi_csv_header, dfmi_csv_encode_batches)
 
 # dfmi_agg_fn (AggregateType, expression.rs:33-40)
 DFMI_AGG_MIN = 0
@@ -206,6 +207,8 @@ EXPORTED = [
     "dfmi_agg_state_free",
     "dfmi_sort_batches",
     "dfmi_format_utf8_batches",
+    "dfmi_csv_header",
+    "dfmi_csv_encode_batches",
     "dfmi_generate_column",  # include/dfmi_datasource.h
     "dfmi_csv_open",
     "dfmi_csv_next",
@@ -441,5 +444,10 @@ def lib() -> C.CDLL:
     L.dfmi_format_utf8_batches.argtypes = [C.c_void_p, P(dfmi_column), P(C.c_int64), C.c_int32, P(dfmi_out_column),
                                            P(C.c_int64), C.c_uint32, P(dfmi_error)]
     L.dfmi_format_utf8_batches.restype = C.c_int32
+    L.dfmi_csv_header.argtypes = [P(dfmi_schema), C.c_void_p, C.c_int64, P(C.c_int64), P(dfmi_error)]
+    L.dfmi_csv_header.restype = C.c_int32
+    L.dfmi_csv_encode_batches.argtypes = [C.c_void_p, P(dfmi_batch), C.c_int32, C.c_void_p, C.c_int64, P(C.c_int64),
+                                          P(C.c_int64), C.c_uint32, P(dfmi_error)]
+    L.dfmi_csv_encode_batches.restype = C.c_int32
     _LIB = L
     return L

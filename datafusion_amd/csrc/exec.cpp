@@ -432,6 +432,7 @@ extern "C" int32_t dfmi_context_create(int32_t device, void* stream, dfmi_contex
 namespace dfmi {
 void sort_scratch_release(dfmi_context* c);
 void format_scratch_release(dfmi_context* c);
+void csv_scratch_release(dfmi_context* c);
 }  // namespace dfmi
 
 extern "C" void dfmi_context_destroy(dfmi_context* c) {
@@ -440,6 +441,7 @@ extern "C" void dfmi_context_destroy(dfmi_context* c) {
     dfmi::host_arena_release(c);
     dfmi::sort_scratch_release(c);
     dfmi::format_scratch_release(c);
+    dfmi::csv_scratch_release(c);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev2) (void)hipEventDestroy(c->ev2);

@@ -54,6 +54,7 @@ struct dfmi_context {
     dfmi::Arena* host_arena = nullptr;  // the host paths' staging arena (host_arena.h; per context: no shared state)
     void* sort_scratch = nullptr;  // sort.cpp's device scratch, kept across dfmi_sort_batches calls
     void* format_scratch = nullptr;  // format.cpp's, kept across dfmi_format_utf8_batches calls
+    void* csv_scratch = nullptr;  // csv_write.cpp's, kept across dfmi_csv_encode_batches calls
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     double last_total_ms = 0, last_main_ms = 0, last_compile_ms = 0;
     bool timed = false;

@@ -199,6 +199,19 @@ class ExecutionContext:
             return self._execute_sort_limit(plan)
         raise ExecutionError("NotImplemented", "unimplemented!() plan %r" % type(plan).__name__)
 
+    def write_csv(self, plan_or_relation, path: str, has_header: bool = True) -> int:
+        """PhysicalPlan::Write { plan, filename, kind: "csv" } (physicalplan.rs:24-29), which the reference
+        never runs, under DFMI_FLAG_EXT_CSV_WRITE: the plan's (or the relation's) batches encoded as CSV on
+        the device, up to `coalesce` batches or 2^20 rows per call, and written to `path`. Returns the rows
+        written. An error from a pull or an encode propagates as it is; the file then holds the header and
+        whole records of a prefix of the result."""
+        from .. import _abi
+        from .csv_writer import write_relation
+        if not (self.flags & _abi.DFMI_FLAG_EXT_CSV_WRITE):
+            raise ExecutionError("NotImplemented", "write_csv needs DFMI_FLAG_EXT_CSV_WRITE")
+        rel = plan_or_relation if isinstance(plan_or_relation, Relation) else self.execute(plan_or_relation)
+        return write_relation(rel, path, has_header, self.device, self.flags, self.coalesce)
+
     def _execute_sort_limit(self, plan) -> Relation:
         """The Sort and Limit arms the reference lacks (context.rs:161
         unimplemented!()), under DFMI_FLAG_EXT_SORT: keys resolved against the

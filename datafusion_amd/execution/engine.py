@@ -322,6 +322,49 @@ class DeviceEngine:
         return [Array(DataType.Utf8, outs[i].length, keeps[i]["data"], keeps[i].get("validity"), keeps[i]["offsets"],
                       outs[i].null_count) for i in range(n)]
 
+    def csv_encode_batches(self, batches: Sequence[RecordBatch], flags: int):
+        """Device batches of one schema as one CSV byte stream (DFMI_FLAG_EXT_CSV_WRITE;
+        the dialect is include/dfmi.h's): dfmi_csv_encode_batches, one call for
+        all of them. Returns (uint8 device tensor of exactly the stream's bytes,
+        batch_ends: the bytes up to the end of each batch). A schema with
+        Float64 or Utf8 columns is measured first (one more call with no data
+        buffer) and allocated exactly; the others are allocated at the types'
+        worst case."""
+        self.drain()
+        L = _abi.lib()
+        batches = [self.to_device(b) for b in batches]
+        nb = len(batches)
+        if nb == 0:
+            return empty_bytes(0, self.device)[:0], []
+        cstructs = []
+        cb = (_abi.dfmi_batch * nb)()
+        for i, b in enumerate(batches):
+            cols = b.columns
+            carr = (_abi.dfmi_column * max(1, len(cols)))(*[column_struct(a) for a in cols])
+            cstructs.append(carr)
+            cb[i].num_columns = len(cols)
+            cb[i].num_rows = b.num_rows()
+            cb[i].columns = carr
+        L.dfmi_context_set_stream(self.ctx, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        ends = (C.c_int64 * nb)()
+        need = C.c_int64(0)
+
+        def call(data, cap):
+            err = _abi.dfmi_error()
+            rc = L.dfmi_csv_encode_batches(self.ctx, cb, nb, data, cap, C.byref(need), ends, flags, C.byref(err))
+            if rc != _abi.DFMI_OK:
+                raise ExecutionError.from_status(rc, err.message.decode("utf-8", errors="replace"))
+
+        types = [c.data_type for c in batches[0].columns]
+        if any(t in (DataType.Float64, DataType.Utf8) for t in types):
+            call(None, 0)  # measure only
+            cap = need.value
+        else:
+            cap = sum(b.num_rows() for b in batches) * (sum(_FORMAT_WORST[t] for t in types) + len(types))
+        out = empty_bytes(max(cap, 8), self.device)
+        call(C.c_void_p(out.data_ptr()), cap)
+        return out[:need.value], [int(e) for e in ends]
+
     def filter_project_host(self, predicate, projections: Optional[Sequence], batch: RecordBatch,
                             flags: int = 0) -> List[Array]:
         """The same pull over a HOST batch through dfmi_filter_project_host:

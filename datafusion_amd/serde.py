@@ -499,12 +499,21 @@ def run_physical_plan(ctx, payload) -> bytes:
     """Worker: a serde_json PhysicalPlan in, the result as an Arrow IPC stream
     out. Interactive runs the plan; Show stops after `count` rows; Write is
     not a worker result (NotImplemented, as the reference has no executor for
-    it). The LogicalPlan runs through ``ctx.execute`` -- Selection /
+    it) -- except under DFMI_FLAG_EXT_CSV_WRITE, where kind "csv" (any letter
+    case) writes the file through ``ctx.write_csv`` and answers with an empty
+    stream of the result schema. The LogicalPlan runs through ``ctx.execute`` -- Selection /
     Projection / Aggregate on the device."""
     from .execution.error import ExecutionError
     pp = from_json(payload, "PhysicalPlan")
     if isinstance(pp, Write):
-        raise ExecutionError("NotImplemented", "PhysicalPlan::Write in a worker")
+        from . import _abi
+        if not (getattr(ctx, "flags", 0) & _abi.DFMI_FLAG_EXT_CSV_WRITE):
+            raise ExecutionError("NotImplemented", "PhysicalPlan::Write in a worker")
+        if pp.kind.lower() != "csv":
+            raise ExecutionError("NotImplemented", 'PhysicalPlan::Write kind "%s"' % pp.kind)
+        rel = ctx.execute(pp.plan)
+        ctx.write_csv(rel, pp.filename)
+        return _write_stream(_pa_schema(rel.schema()), [])
     rel = ctx.execute(pp.plan)
     limit = pp.count if isinstance(pp, Show) else None
     pbatches, rows, pschema = [], 0, None

@@ -457,6 +457,36 @@ typedef struct dfmi_expr_node {
  *             "device program limit: CAST to Utf8 output of 2^31 or more bytes".
  * One flag bit, one new entry point, no struct change: DFMI_ABI_VERSION stays 4. */
 
+#define DFMI_FLAG_EXT_CSV_WRITE    0x2000u
+/* CSV output: PhysicalPlan::Write { plan, filename, kind } (physicalplan.rs:24-29,
+ * "Execute a logical plan and write the output to a file"), which the reference
+ * defines and never runs. Result batches are encoded as CSV on the device by
+ * dfmi_csv_encode_batches below; dfmi_csv_header gives the header line.
+ * Build-defined, parity unpinned: arrow 0.12 has no CSV writer. The dialect is
+ * "what the native CSV reader (include/dfmi_datasource.h) and the reference's
+ * CsvDataSource read back to the same values":
+ *   records:  one per row, in row order and batch order; fields separated by
+ *             ','; every record ends with '\n', the last one too; no '\r' is
+ *             ever written as a line end;
+ *   Boolean, integers, floats: exactly the bytes of CAST(e AS Utf8) under
+ *             DFMI_FLAG_EXT_CAST_UTF8 above -- "true" / "false"; digits with a
+ *             leading '-'; the shortest digits that read back in the value's own
+ *             width, never an exponent; "-0", "inf", "-inf", "NaN";
+ *   null:     a null of any type is an empty field. A Utf8 null and the empty
+ *             string are the same bytes (the reader gives "" for both);
+ *   Utf8:     the bytes as they are. The field is quoted exactly when it holds
+ *             '"', ',', '\n' or '\r'; inside quotes a '"' is doubled. 0x00 and
+ *             0x80-0xFF are ordinary bytes; a space never forces quotes;
+ *   empty record: a record of ONE column whose only field is empty (a null, an
+ *             empty string) is written as `""`: the reader skips empty records,
+ *             reads `""` as the empty string and, in a numeric column, as null;
+ *   no validity: a column without validity (every batch after a Selection) has
+ *             no nulls: a slot is formatted from its raw bits -- the rule of
+ *             Utf8 `=` and of CAST to Utf8;
+ *   header:   the field names joined by ',' and ended by '\n', under the same
+ *             quoting rule (and the same one-column rule).
+ * One flag bit, two new entry points, no struct change: DFMI_ABI_VERSION stays 4. */
+
 /* Signature of a built-in scalar function, for a binding's
  * SchemaProvider::get_function_meta (sqlplanner.rs:330-350 casts each
  * argument to arg_types[i]). Returns 0 and fills *num_args, *return_type and
@@ -954,6 +984,45 @@ int32_t dfmi_sort_batches(dfmi_context* ctx, const dfmi_batch* inputs, int32_t n
 int32_t dfmi_format_utf8_batches(dfmi_context* ctx, const dfmi_column* columns, const int64_t* num_rows,
                                  int32_t num_columns, dfmi_out_column* outputs, int64_t* data_lengths,
                                  uint32_t flags, dfmi_error* err);
+
+/* ---------------------------------------------------------------------------
+ * CSV output (DFMI_FLAG_EXT_CSV_WRITE; the dialect is specified at the flag).
+ *
+ * dfmi_csv_header: the header line of `schema` into the HOST buffer `out`. Host
+ * only: no context, no flag. *length is always written; capacity below it is
+ * DFMI_ERR_CAPACITY with no byte written; out == NULL measures only. A NULL
+ * schema, a schema without fields or a NULL name is DFMI_ERR_INVALID_ARGUMENT.
+ *
+ * dfmi_csv_encode_batches: `num_batches` device batches that share one
+ * column-type list (0-row batches allowed, sliced columns through
+ * dfmi_column.offset) as ONE byte stream of records in the device buffer
+ * `data`, all columns of a row interleaved -- all the batches of a coalesced
+ * pull in one call: the kernels run once over every batch together.
+ *   *data_length   the bytes the call needs -- always written, also when the
+ *                  call fails on a capacity or on the byte limit;
+ *   batch_ends[i]  the bytes up to the end of batch i's last record (may be
+ *                  NULL);
+ *   measure mode   with data == NULL the call writes *data_length and
+ *                  batch_ends and no byte. A caller whose schema holds Float64
+ *                  or Utf8 columns measures, allocates exactly and calls again;
+ *                  the others allocate rows * (the sum of the per-type worst
+ *                  cases at dfmi_format_utf8_batches above + the column count).
+ * Errors: data_capacity below the need is DFMI_ERR_CAPACITY (*data_length set,
+ * no byte written); 2^31 or more rows in the call, 2^31 or more output bytes or
+ * more than 256 columns DFMI_ERR_NOT_IMPLEMENTED "device program limit: ...";
+ * a call without the flag DFMI_ERR_NOT_IMPLEMENTED; batches whose column types
+ * differ, a type outside Boolean .. Utf8, a batch without columns, a length
+ * that differs from num_rows or a NULL buffer DFMI_ERR_INVALID_ARGUMENT.
+ * Synchronous. The context keeps the call's scratch (8 bytes per input row,
+ * rounded up to 256 rows per batch, 4 more per row and Utf8 column, plus the
+ * scan's) for later calls and frees it in dfmi_context_destroy.
+ * ------------------------------------------------------------------------- */
+int32_t dfmi_csv_header(const dfmi_schema* schema, uint8_t* out /* host */, int64_t capacity,
+                        int64_t* length, dfmi_error* err);
+int32_t dfmi_csv_encode_batches(dfmi_context* ctx, const dfmi_batch* inputs, int32_t num_batches,
+                                uint8_t* data /* device; NULL: measure only */, int64_t data_capacity,
+                                int64_t* data_length, int64_t* batch_ends /* [num_batches], may be NULL */,
+                                uint32_t flags, dfmi_error* err);
 
 /* ---------------------------------------------------------------------------
  * Multi-GPU. The reference is single-threaded (context.rs:33);
