@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "agg_state.h"
+#include "batch_table.h"
 #include "launch_args.h"
 #include "slice.h"
 
@@ -38,9 +39,6 @@ namespace {
 
 std::atomic<long> g_query_launches{0};
 
-// Per-batch header of the coalesced launch (exec.cpp's layout): word 24 the error word.
-constexpr size_t kBatchHdr = 256;
-constexpr int kBatchHdrErrWord = 24;
 // Packed input bytes one host call stages at a time (larger calls are split at batch boundaries).
 constexpr size_t kStageBudget = (size_t)64 << 20;
 
@@ -51,14 +49,6 @@ struct Failure {
     bool failed() const { return batch >= 0; }
 };
 
-Fail device_fail(int kind) {
-    if (kind == ERRK_DIV_ZERO) return Fail{DFMI_ERR_DIVIDE_BY_ZERO, "DivideByZero"};
-    if (is_cast_digits(kind))
-        return Fail{DFMI_ERR_NOT_IMPLEMENTED, cast_digits_message(kind)};
-    return Fail{DFMI_ERR_PANIC, kind == ERRK_REM_OVERFLOW ? "attempt to calculate the remainder with overflow"
-                                                          : "attempt to divide with overflow"};
-}
-
 // Batches [0, nb) through ONE launch of st's batched kernel (ungrouped, or
 // the key-window kernel over the window gbase / gwidth). The accumulators
 // hold partial sums of every batch afterwards, also of those behind the
@@ -67,101 +57,35 @@ Failure run_batched(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* p
                     uint32_t flags, const AggDiag& diag) {
     Failure R;
     if (nb <= 0) return R;
-    const int ncols = ins[0].num_columns;
-    int64_t maxn = 0;
-    for (int32_t b = 0; b < nb; ++b) maxn = std::max<int64_t>(maxn, ins[b].num_rows);
-    // the shape batch: shared types, nullable where any batch has nulls (the
-    // plan reads types and nullability only)
-    static const uint64_t kDummy[2] = {0, 0};
-    std::vector<dfmi_column> shape(ncols);
-    std::vector<char> nullable(ncols, 0);
-    for (int i = 0; i < ncols; ++i) {
-        for (int32_t b = 0; b < nb; ++b)
-            if (ins[b].columns[i].validity && ins[b].columns[i].null_count > 0) nullable[i] = 1;
-        dfmi_column& c = shape[i];
-        c = ins[0].columns[i];
-        c.length = maxn;
-        c.offset = 0;
-        c.validity = nullable[i] ? (const uint8_t*)kDummy : nullptr;
-        c.null_count = nullable[i] ? 1 : 0;
-        c.values = kDummy;
-        c.offsets = (const int32_t*)kDummy;
-    }
-    const dfmi_batch shape_batch{ncols, 0, maxn, shape.data()};
+    const ShapeBatch S(ins, nb);
     AggBuilt B;
-    build_batch_plan(st, pred, &shape_batch, flags, diag, B, false);
+    build_batch_plan(st, pred, &S.view, flags, diag, B, false);
     jit::Launch& X = B.X;
     X.batched = true;
     X.M = 1;  // (no sub-tiles in the batched form)
-    const int64_t tile_rows = (int64_t)X.BLOCK * X.K;
-    std::vector<int64_t> first(nb), tiles(nb);
-    int64_t T = 0;
-    for (int32_t b = 0; b < nb; ++b) {
-        tiles[b] = (ins[b].num_rows + tile_rows - 1) / tile_rows;
-        first[b] = T;
-        T += tiles[b];
-    }
-    if (T > 0x7fffffff) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "batch too large"};
-    const uint8_t* host_hdr = nullptr;
+    const TileLayout L(ins, nb, (int64_t)X.BLOCK * X.K);
+    const int64_t T = L.T;
+    BatchTable table(X, S, L, nb, 0);  // (no output slots: the kernel accumulates into the state)
     if (T > 0) {
         HIP_TRY(hipSetDevice(ctx->device));
         hipStream_t stream = ctx->stream;
         ctx->timed = false;
         ctx->last_compile_ms = 0;
         const hipFunction_t fn = query_kernel(ctx, B.plan, X, B.se);
-        const int NPW = jit::batch_words(X, 0);
-        const size_t table_bytes = (size_t)nb * NPW * 8, meta_bytes = table_bytes + (size_t)T * 4;
-        const size_t hdr_bytes = (size_t)nb * kBatchHdr;
-        ctx->host_bmeta.resize(meta_bytes, kCtxPinned);
-        ctx->host_bhdr.resize(hdr_bytes, kCtxPinned);
-        uint8_t* const bmeta = (uint8_t*)ctx->bmeta.reserve(meta_bytes, kCtxDev);
-        uint8_t* const bhdr = (uint8_t*)ctx->bhdr.reserve(hdr_bytes, kCtxDev);
-        bool need_ones = false;
-        for (int i = 0; i < ncols && !need_ones; ++i)
-            if (nullable[i])
-                for (int32_t b = 0; b < nb; ++b)
-                    if (!(ins[b].columns[i].validity && ins[b].columns[i].null_count > 0)) need_ones = true;
-        if (need_ones) {  // the all-valid bitmap of the batches without nulls in a column others have them in
-            const size_t nbm = (size_t)((maxn + 63) / 64 * 8 + 64);
-            if (ctx->ones.cap < nbm) {
-                ctx->ones.reserve(nbm, kCtxDev);
-                HIP_TRY(hipMemsetAsync(ctx->ones.p, 0xff, ctx->ones.cap, stream));
-            }
-        }
-        uint64_t* tab = (uint64_t*)ctx->host_bmeta.p;
-        int32_t* tile_batch = (int32_t*)(ctx->host_bmeta.p + table_bytes);
-        for (int32_t b = 0; b < nb; ++b) {
-            const dfmi_batch& in = ins[b];
-            uint64_t* row = tab + (size_t)b * NPW;
-            memset(row, 0, (size_t)NPW * 8);
-            row[0] = (uint64_t)in.num_rows;
-            row[1] = (uint64_t)tiles[b] | ((uint64_t)first[b] << 32);
-            row[2] = (uint64_t)(bhdr + (size_t)b * kBatchHdr);
-            row[3] = (uint64_t)(bhdr + (size_t)b * kBatchHdr + kBatchHdrErrWord * 8);
-            for (size_t sl = 0; sl < X.num_cols.size(); ++sl) {
-                const int col = X.num_cols[sl];
-                const dfmi_column& c = in.columns[col];
-                const int w = dfmi::type_width(c.type);
-                if (in.num_rows > 0 && !c.values) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "column values pointer is NULL"};
-                if (w && ((uintptr_t)c.values & (w - 1)))
-                    throw Fail{DFMI_ERR_INVALID_ARGUMENT, "column values must be aligned to their width"};
-                row[jit::batch_slot_col((int)sl)] = (uint64_t)c.values;
-                row[jit::batch_slot_col((int)sl) + 1] =
-                    !nullable[col] ? 0 : (uint64_t)((c.validity && c.null_count > 0) ? c.validity : ctx->ones.p);
-            }
-            for (int64_t t = 0; t < tiles[b]; ++t) tile_batch[first[b] + t] = b;
-        }
-        HIP_TRY(hipMemcpyAsync(bmeta, ctx->host_bmeta.p, meta_bytes, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemsetAsync(bhdr, 0, hdr_bytes, stream));
+        table.in_context(ctx);
+        table.ones = ensure_ones(ctx, S, ins, nb, stream);
+        for (int32_t b = 0; b < nb; ++b) table.write_row(b, ins[b]);
+        HIP_TRY(hipMemcpyAsync(table.dev_meta, table.host_meta, table.meta_bytes, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(table.dev_hdr, 0, table.hdr_bytes, stream));
         Args A;
         memset(&A, 0, sizeof A);
-        A.n_rows = maxn;
+        A.n_rows = S.maxn;
         A.n_tiles = (int)T;
         bind_literals(A, X);
         const WsLease ws = ws_acquire(ctx, 0, stream);
         bind_workspace(A, ws);
-        A.tile_batch = (const int*)(bmeta + table_bytes);
-        A.batch_ptrs = (void* const*)bmeta;
+        A.tile_batch = (const int*)(table.dev_meta + table.table_bytes);
+        A.batch_ptrs = (void* const*)table.dev_meta;
         A.agg = st->acc.as<unsigned long long>();
         A.gbase = st->win_base;
         A.gwidth = st->win_width;
@@ -170,23 +94,17 @@ Failure run_batched(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* p
         count_query_launch();
         ws_commit(ctx, ws);
         if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev1, stream));
-        HIP_TRY(hipMemcpyAsync(ctx->host_bhdr.p, bhdr, hdr_bytes, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(ctx->host_bhdr.p, table.dev_hdr, table.hdr_bytes, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        if (ctx->timing) {
-            float m1 = 0;
-            (void)hipEventElapsedTime(&m1, ctx->ev0, ctx->ev1);
-            ctx->last_main_ms = ctx->last_total_ms = m1;
-            ctx->timed = true;
-        }
-        host_hdr = ctx->host_bhdr.p;
+        if (ctx->timing) read_timing(ctx, false);
     }
     // ---- in batch order: the first batch dfmi_aggregate_batch would have failed on
     const Err& se = B.se;
     for (int32_t b = 0; b < nb; ++b) {
         uint64_t dev_key = ~0ull;
         int dev_kind = 0;
-        if (host_hdr && ins[b].num_rows > 0)
-            decode_err_word(((const uint64_t*)(host_hdr + (size_t)b * kBatchHdr))[kBatchHdrErrWord], dev_key, dev_kind);
+        if (table.host_hdr && ins[b].num_rows > 0)
+            decode_err_word(batch_hdr(table.host_hdr, b)[kBatchHdrErr], dev_key, dev_kind);
         if (dev_kind == ERRK_CAPACITY) {  // a key outside the window the pre-pass found: cannot happen
             R.batch = b;
             R.fail = Fail{DFMI_ERR_DEVICE, "GROUP BY key outside the batch's key window"};

@@ -38,51 +38,27 @@ namespace dfmi {
 namespace agg {
 
 // Static errors, slots and tile shape of one aggregate batch (AggBuilt,
-// agg_state.h: the filtered form of exec.cpp's build_plan: FilterRelation::next,
-// then each argument over the filtered batch in aggregate order).
+// agg_state.h: the filtered form of exec_plan.cpp's build_plan, over the same
+// pieces, exec_internal.h: FilterRelation::next, then each argument over the
+// filtered batch in aggregate order).
 void build_agg_plan(const dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* in, uint32_t flags,
                     const AggDiag& diag, AggBuilt& B, bool low_sel) {
     Err& se = B.se;
     jit::Launch& X = B.X;
-    const int64_t n = in->num_rows;
-    const int ncols = in->num_columns;
-    auto check_schema = [&](const dfmi_program* p) {
-        if ((int)p->schema_types.size() != ncols)
-            throw Fail{DFMI_ERR_INVALID_ARGUMENT, "batch does not match the compiled schema"};
-        for (int i = 0; i < ncols; ++i)
-            if (p->schema_types[i] != in->columns[i].type)
-                throw Fail{DFMI_ERR_INVALID_ARGUMENT, "batch column type does not match the schema"};
-    };
-    if (pred) check_schema(pred);
-    if (st->grouped) check_schema(&st->key);
-    for (const dfmi_aggregate* a : st->aggs) check_schema(&a->arg);
-    for (int i = 0; i < ncols; ++i)
-        if (in->columns[i].length != n) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "ragged batch"};
-    const int P = pred ? pred->length : 0;
-    if (pred) {
-        for (const IrNode& nd : pred->ir)
-            if (nd.rt_code) se.offer((uint64_t)nd.ordinal << 44, nd.rt_code, nd.rt_msg);
-        if (pred->type != DFMI_TYPE_BOOLEAN)
-            se.offer((uint64_t)P << 44, DFMI_ERR_EXECUTION, "Filter expression did not evaluate to boolean");
-        for (int i = 0; i < ncols; ++i)
-            if (!gatherable(in->columns[i].type, flags)) {
-                se.offer((uint64_t)(P + 1) << 44, DFMI_ERR_EXECUTION,
-                         std::string("filter not supported for ") + type_debug(in->columns[i].type));
-                break;
-            }
-    }
-    int base = P + 2, nf = 0;
+    if (pred) check_schema(pred, in);
+    if (st->grouped) check_schema(&st->key, in);
+    for (const dfmi_aggregate* a : st->aggs) check_schema(&a->arg, in);
+    check_not_ragged(in);
+    int base = offer_filter_errors(pred, in, flags, se), nf = 0;
     if (st->grouped) {  // the group key is evaluated before the aggregates
-        for (const IrNode& nd : st->key.ir)
-            if (nd.rt_code) se.offer((uint64_t)(base + nd.ordinal) << 44, nd.rt_code, nd.rt_msg);
+        offer_program_errors(&st->key, base, se);
         B.plan.gkey = &st->key;
         B.plan.gkey_ord = base;
         B.plan.gslots = st->gslots;
         base += st->key.length;
     }
     for (const dfmi_aggregate* a : st->aggs) {
-        for (const IrNode& nd : a->arg.ir)
-            if (nd.rt_code) se.offer((uint64_t)(base + nd.ordinal) << 44, nd.rt_code, nd.rt_msg);
+        offer_program_errors(&a->arg, base, se);
         jit::AggSpec s;
         s.fn = acc_fn(*a);  // (an AVG accumulates as a SUM, a Utf8 MIN / MAX as a COUNT: the same kernel source and cache key)
         s.prog = &a->arg;
@@ -92,33 +68,15 @@ void build_agg_plan(const dfmi_agg_state* st, const dfmi_program* pred, const df
         B.plan.aggs.push_back(s);
         base += a->arg.length;
     }
-    if (base >= (1 << 19)) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "device program limit: expressions too long"};
+    check_ordinal_limit(base);
     if (nf > 4) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "device program limit: more than 4 floating-point SUMs"};
     B.plan.pred = pred;
     X.in = in;
-    auto reg_num = [&](int col, std::vector<int>& phase) {
-        for (size_t i = 0; i < X.num_cols.size(); ++i)
-            if (X.num_cols[i] == col) return;
-        X.num_cols.push_back(col);
-        phase.push_back((int)X.num_cols.size() - 1);
-    };
-    auto reg_prog = [&](const dfmi_program* p, std::vector<int>& phase) {
-        for (const IrNode& nd : p->ir) {
-            if (nd.kind != IR_COL) continue;
-            if (nd.type == DFMI_TYPE_UTF8) {
-                bool have = false;
-                for (int c : X.utf8_cols) have |= c == nd.col;
-                if (!have) X.utf8_cols.push_back(nd.col);
-            } else if (dfmi::type_width(nd.type) || nd.type == DFMI_TYPE_BOOLEAN) {
-                reg_num(nd.col, phase);
-            }
-        }
-    };
-    if (pred) reg_prog(pred, X.pred_slots);
-    if (st->grouped) reg_prog(&st->key, X.proj_slots);
-    for (const dfmi_aggregate* a : st->aggs) reg_prog(&a->arg, X.proj_slots);
-    if ((int)X.num_cols.size() > kArgCols || X.utf8_cols.size() > (size_t)kArgUtf8)
-        throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "device program limit: too many input columns"};
+    Slots slots{X};
+    if (pred) slots.prog(pred, X.pred_slots);
+    if (st->grouped) slots.prog(&st->key, X.proj_slots);
+    for (const dfmi_aggregate* a : st->aggs) slots.prog(&a->arg, X.proj_slots);
+    slots.check_limit(kArgCols, kArgUtf8);
     const size_t nload = X.num_cols.size();
     X.BLOCK = 512;
     X.K = nload <= 4 ? 8 : (nload <= 8 ? 4 : 2);
@@ -135,21 +93,14 @@ void build_agg_plan(const dfmi_agg_state* st, const dfmi_program* pred, const df
     if (can_sub && low_sel && in->num_rows >= (1 << 22)) X.M = 4;
     if (diag.subtiles) X.M = can_sub ? std::max(1, std::min(16, atoi(diag.subtiles))) : 1;  // diagnostics: force M
     if (X.K < 1 || X.K > 32) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "bad tile shape"};
-    const int64_t tile_rows = (int64_t)X.BLOCK * X.K * X.M;
-    B.n_tiles = (n + tile_rows - 1) / tile_rows;
-    if (B.n_tiles > 0x7fffffff) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "batch too large"};
+    B.n_tiles = tiles_of(in->num_rows, (int64_t)X.BLOCK * X.K * X.M);
 }
 
 // ... for a batch: a device program limit yields to the static error the
 // reference raises first.
 void build_batch_plan(const dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* in, uint32_t flags,
                       const AggDiag& diag, AggBuilt& B, bool low_sel) {
-    try {
-        build_agg_plan(st, pred, in, flags, diag, B, low_sel);
-    } catch (const Fail& f) {
-        if (f.code == DFMI_ERR_NOT_IMPLEMENTED && B.se.set) throw Fail{B.se.code, B.se.msg};
-        throw;
-    }
+    static_error_first(B.se, [&] { build_agg_plan(st, pred, in, flags, diag, B, low_sel); });
 }
 
 }  // namespace agg
@@ -588,25 +539,14 @@ extern "C" int32_t dfmi_aggregate_batch(dfmi_context* ctx, dfmi_agg_state* st, c
                 ctx->sel_hint[hint_key] = sampled ? (double)sel / (double)sampled : 1.0;
             }
             decode_err_word(ew, dev_key, dev_kind);
-            float m1 = 0, m2 = 0;
-            (void)hipEventElapsedTime(&m1, ctx->ev0, ctx->ev1);
-            (void)hipEventElapsedTime(&m2, ctx->ev0, ctx->ev2);
-            ctx->last_main_ms = m1;
-            ctx->last_total_ms = m2;
-            ctx->timed = true;
+            read_timing(ctx, true);
         }
         if (st->grouped && n > 0) st->dirty = true;
         Fail fail{DFMI_OK, ""};
         if (dev_kind == ERRK_CAPACITY)  // a key outside the window the pre-pass found: cannot happen
             fail = Fail{DFMI_ERR_DEVICE, "GROUP BY key outside the batch's key window"};
         else if (dev_kind && (!se.set || dev_key < se.key))
-            fail = dev_kind == ERRK_DIV_ZERO
-                       ? Fail{DFMI_ERR_DIVIDE_BY_ZERO, "DivideByZero"}
-                   : (is_cast_digits(dev_kind))
-                       ? Fail{DFMI_ERR_NOT_IMPLEMENTED, cast_digits_message(dev_kind)}
-                       : Fail{DFMI_ERR_PANIC, dev_kind == ERRK_REM_OVERFLOW
-                                                  ? "attempt to calculate the remainder with overflow"
-                                                  : "attempt to divide with overflow"};
+            fail = device_fail(dev_kind);
         else if (se.set)
             fail = Fail{se.code, se.msg};
         if (fail.code != DFMI_OK) {

@@ -1,4 +1,4 @@
-// How a caller of the coalesced-batches launch (exec.cpp) stages its small
+// How a caller of the coalesced-batches launch (exec_batches.cpp) stages its small
 // per-call data: the host-batches entry point (host_batches.cpp) moves its
 // packed inputs and the batch table with ONE H2D copy (none for small calls,
 // whose kernel reads them from pinned memory), and the outputs with the

@@ -1,6 +1,7 @@
-// Internals shared by the execution entry points (exec.cpp: filter +
-// project, aggregate.cpp and agg_hash.cpp: the aggregate extension): the
-// context, the workspace layout, error plumbing.
+// Internals shared by the execution entry points (exec.cpp and
+// exec_batches.cpp: filter + project, aggregate.cpp and agg_hash.cpp: the
+// aggregate extension): the context (context.cpp), the workspace layout,
+// error plumbing.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,7 @@
 #include <cstdio>
 #include <string>
 #include <unordered_map>
+#include <vector>
 
 #include "buffers.h"
 #include "col_layout.h"
@@ -68,7 +70,7 @@ struct dfmi_context {
     // bitmap for batches without validity in a column others have it for
     dfmi::DevBuf bmeta, bhdr, ones;
     dfmi::HostBuf<uint8_t> host_bmeta, host_bhdr;
-    // selectivity of each query shape's last large batch (exec.cpp
+    // selectivity of each query shape's last large batch (exec_plan.cpp
     // kSubtileMinRows): picks the sub-tile kernel for low selectivity
     std::unordered_map<uint64_t, double> sel_hint;
     // ... and the mean bytes of its first Utf8 output's selected strings
@@ -184,6 +186,137 @@ inline void ws_commit(dfmi_context* ctx, const WsLease& l) {
     ctx->parity = q;
     ctx->ws_valid = true;
 }
+
+// ---------------------------------------------------------------- planning
+// What the filter + project plan (exec_plan.cpp) and the aggregate plan
+// (aggregate.cpp build_agg_plan) have in common: the schema checks, the
+// static errors of a predicate and of a program at an ordinal base (the
+// reference's evaluation order: FilterRelation::next filter.rs:46-72, then
+// each expression over the filtered batch), the input slot registration and
+// the limits both kernels share.
+
+inline void check_schema(const dfmi_program* p, const dfmi_batch* in) {
+    if ((int)p->schema_types.size() != in->num_columns)
+        throw Fail{DFMI_ERR_INVALID_ARGUMENT, "batch does not match the compiled schema"};
+    for (int i = 0; i < in->num_columns; ++i)
+        if (p->schema_types[i] != in->columns[i].type)
+            throw Fail{DFMI_ERR_INVALID_ARGUMENT, "batch column type does not match the schema"};
+}
+
+inline void check_not_ragged(const dfmi_batch* in) {
+    for (int i = 0; i < in->num_columns; ++i)
+        if (in->columns[i].length != in->num_rows) throw Fail{DFMI_ERR_INVALID_ARGUMENT, "ragged batch"};
+}
+
+// The errors every evaluation of `prog` raises, its nodes' ordinals from `base`.
+inline void offer_program_errors(const dfmi_program* prog, int base, Err& se) {
+    for (const IrNode& nd : prog->ir)
+        if (nd.rt_code) se.offer((uint64_t)(base + nd.ordinal) << 44, nd.rt_code, nd.rt_msg);
+}
+
+// ... and a Selection's: the predicate's own nodes, then its type (ordinal
+// P), then the columns filter() cannot gather (P + 1). The expressions behind
+// it start at ordinal P + 2, which is returned (2 without a predicate).
+inline int offer_filter_errors(const dfmi_program* pred, const dfmi_batch* in, uint32_t flags, Err& se) {
+    if (!pred) return 2;
+    const int P = pred->length;
+    offer_program_errors(pred, 0, se);
+    if (pred->type != DFMI_TYPE_BOOLEAN)
+        se.offer((uint64_t)P << 44, DFMI_ERR_EXECUTION, "Filter expression did not evaluate to boolean");
+    for (int i = 0; i < in->num_columns; ++i)
+        if (!gatherable(in->columns[i].type, flags)) {
+            se.offer((uint64_t)(P + 1) << 44, DFMI_ERR_EXECUTION,
+                     std::string("filter not supported for ") + type_debug(in->columns[i].type));
+            break;
+        }
+    return P + 2;
+}
+
+// `end`: the ordinal behind the plan's last expression (the error key holds 19 bits of it).
+inline void check_ordinal_limit(int end) {
+    if (end >= (1 << 19)) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "device program limit: expressions too long"};
+}
+
+// Input columns to the launch's slots, each column once, in the order asked
+// for: predicate columns first, then the ones only the outputs read.
+struct Slots {
+    jit::Launch& X;
+    void num(int col, std::vector<int>& phase) {
+        for (int c : X.num_cols)
+            if (c == col) return;
+        X.num_cols.push_back(col);
+        phase.push_back((int)X.num_cols.size() - 1);
+    }
+    int utf8(int col) {
+        for (size_t i = 0; i < X.utf8_cols.size(); ++i)
+            if (X.utf8_cols[i] == col) return (int)i;
+        X.utf8_cols.push_back(col);
+        return (int)X.utf8_cols.size() - 1;
+    }
+    void prog(const dfmi_program* p, std::vector<int>& phase) {
+        for (const IrNode& nd : p->ir) {
+            if (nd.kind != IR_COL) continue;
+            if (nd.type == DFMI_TYPE_UTF8) utf8(nd.col);
+            else if (dfmi::type_width(nd.type) || nd.type == DFMI_TYPE_BOOLEAN) num(nd.col, phase);
+        }
+    }
+    void check_limit(int max_num, int max_utf8) const {  // (the kernel's Args: kArgCols, kArgUtf8)
+        if ((int)X.num_cols.size() > max_num || (int)X.utf8_cols.size() > max_utf8)
+            throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "device program limit: too many input columns"};
+    }
+};
+
+// Tiles of `tile_rows` rows that cover n rows (a launch's grid: 31 bits).
+inline int64_t tiles_of(int64_t n, int64_t tile_rows) {
+    const int64_t t = (n + tile_rows - 1) / tile_rows;
+    if (t > 0x7fffffff) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "batch too large"};
+    return t;
+}
+
+// A device limit (NotImplemented) found while planning is reported only when
+// the plan raises none of the reference's own errors first: those come
+// earlier in its evaluation order (and stand for what it would report).
+template <class F>
+inline void static_error_first(const Err& se, F&& plan) {
+    try {
+        plan();
+    } catch (const Fail& f) {
+        if (f.code == DFMI_ERR_NOT_IMPLEMENTED && se.set) throw Fail{se.code, se.msg};
+        throw;
+    }
+}
+
+// ------------------------------------------- the filter + project plan
+// (exec_plan.cpp), as its launch sites use it: dfmi_filter_project (exec.cpp)
+// and the coalesced form (exec_batches.cpp).
+
+// Everything about one call that does not need the device: static errors,
+// output metadata, the jit plan and the column slot tables.
+struct Built {
+    Err se;
+    jit::Plan plan;
+    jit::Launch X;
+    bool any_kernel_out = false;
+    int64_t n_tiles = 0;
+    bool low_sel = false;  // in: this query shape selected few rows last time (dfmi_context::sel_hint)
+    bool high_sel = false;  // in: ... or at least kLowSel of them
+    bool ring_ok = false;  // in: ... selected many rows with short Utf8 strings (the ring-staged gather)
+    bool long_utf8 = false;  // in: ... selected long Utf8 strings (the long per-lane fallback copy)
+};
+
+// Fills B (its hint flags are inputs) and the outputs' metadata; a static
+// error wins over a device limit (static_error_first).
+void build_plan(const dfmi_program* pred, const dfmi_program* const* projs, int32_t np, const dfmi_batch* in,
+                dfmi_out_column* outs, uint32_t flags, Built& B);
+
+// What the query shape's last large batch on this context selected, into B's
+// hint flags; the shape's key, 0 when the batch is too small to keep one.
+uint64_t sel_hint_lookup(const dfmi_context* ctx, const dfmi_program* pred, const dfmi_program* const* projs,
+                         int32_t np, const dfmi_batch* in, uint32_t flags, Built& B);
+// ... and what this batch selected (out_rows of n rows, utf8_bytes in its
+// first Utf8 output), for the shape's next one.
+void sel_hint_update(dfmi_context* ctx, uint64_t key, const jit::Launch& X, int64_t n, int64_t out_rows,
+                     uint64_t utf8_bytes);
 
 }  // namespace xi
 }  // namespace dfmi

@@ -229,7 +229,7 @@ void hb_layout(const dfmi_program* pred, const dfmi_program* const* projs, int32
     Lo.OB = align256(std::max<size_t>(out_bytes, 256));
     Lo.H = align256((size_t)nb * 256);
     Lo.IB = align256(std::max<size_t>(in_bytes, 256));
-    size_t MB = 256;  // bound on the launch's batch table + tile map (exec.cpp)
+    size_t MB = 256;  // bound on the launch's batch table + tile map (batch_table.h)
     for (int32_t b = 0; b < nb; ++b)
         MB += (size_t)(4 + 3 * ncols + 5 * nout) * 8 + (size_t)((ins[b].num_rows + 63) / 64 + 1) * 4;
     Lo.MB = align256(MB);

@@ -95,7 +95,7 @@ struct TileShape {
     // (profiles/r05/c3_light_copy_ab2.log, long_utf8.log)
     int light_copy = 1;
     // Utf8 gather's per-lane fallback for long strings (long_copy): 64 bytes
-    // in flight per lane (exec.cpp: the query's last large batch selected
+    // in flight per lane (exec_plan.cpp: the query's last large batch selected
     // strings of >= kLongLen bytes on average)
     int long_copy = 0;
     // gather == 6 (utf8_gather_direct): slices whose loads go out together

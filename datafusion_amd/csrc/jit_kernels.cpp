@@ -726,7 +726,7 @@ void emit_sparse_pass(const FilterCtx& c) {
 // output pass revisits the sub-tiles with selected rows, reloading the Utf8
 // offsets and column values they need. (a numeric predicate loads its columns
 // per sub-tile; its output pass reloads the columns the outputs read for the
-// selected rows only -- chosen for low selectivity, exec.cpp)
+// selected rows only -- chosen for low selectivity, exec_plan.cpp)
 void generate_filter_subtiles(const FilterCtx& c) {
     std::ostream& o = c.o;
     const Launch& X = c.X;

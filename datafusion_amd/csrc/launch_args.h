@@ -18,6 +18,16 @@ inline const char* cast_digits_message(int kind) {
 }
 inline bool is_cast_digits(int kind) { return kind == ERRK_CAST_DIGITS || kind == ERRK_CAST_DIGITS_F32; }
 
+// The reference's error (or the device limit) behind an arithmetic or CAST
+// ERRK_ kind of a device error word. A look-back timeout and ERRK_CAPACITY
+// are the launch sites' own: they mean different things to each.
+inline Fail device_fail(int kind) {
+    if (kind == ERRK_DIV_ZERO) return Fail{DFMI_ERR_DIVIDE_BY_ZERO, "DivideByZero"};
+    if (kind == ERRK_REM_OVERFLOW) return Fail{DFMI_ERR_PANIC, "attempt to calculate the remainder with overflow"};
+    if (is_cast_digits(kind)) return Fail{DFMI_ERR_NOT_IMPLEMENTED, cast_digits_message(kind)};
+    return Fail{DFMI_ERR_PANIC, "attempt to divide with overflow"};
+}
+
 namespace xi {
 
 // The numeric and Utf8 input columns of X's slots.
@@ -78,6 +88,17 @@ inline void launch_query(hipFunction_t fn, unsigned grid, unsigned block, Args& 
     size_t asz = sizeof A;
     void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
     HIP_TRY(hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, 0, stream, nullptr, cfg));
+}
+
+// The launch's device times from the context's events: ev0 .. ev1 the
+// kernels, ev0 .. ev2 (where the call recorded it) with the header's copy.
+inline void read_timing(dfmi_context* ctx, bool has_ev2) {
+    float m1 = 0, m2 = 0;
+    (void)hipEventElapsedTime(&m1, ctx->ev0, ctx->ev1);
+    if (has_ev2) (void)hipEventElapsedTime(&m2, ctx->ev0, ctx->ev2);
+    ctx->last_main_ms = m1;
+    ctx->last_total_ms = has_ev2 ? m2 : m1;
+    ctx->timed = true;
 }
 
 // The header's error word (0: none): its evaluation-order key and ERRK_ kind.

@@ -601,7 +601,7 @@ def subtile_query(seed):
 
 def takes_subtile_form(pred, projs):
     """The numeric sub-tile kernel takes a query with a predicate over at
-    least one column and no Utf8 column anywhere (exec.cpp)."""
+    least one column and no Utf8 column anywhere (exec_plan.cpp)."""
     if pred is None:
         return False
     cols = [e for tree in [pred] + list(projs) for e in postfix(tree) if isinstance(e, Column)]

@@ -687,7 +687,7 @@ def test_utf8_long_copy_variant(monkeypatch, mode):
 def test_utf8_long_strings_choose_long_copy():
     """A large batch of long strings (30-300 bytes): its first call records
     the selected bytes per row, the next call of the same query compiles the
-    long-copy fallback (exec.cpp kLongLen). Both against the oracle, including
+    long-copy fallback (exec_plan.cpp kLongLen). Both against the oracle, including
     a data buffer that ends exactly at the last string's last byte (the
     loads past a string's end stop at offs[n_rows])."""
     import torch
@@ -723,7 +723,7 @@ def test_utf8_long_strings_choose_long_copy():
 def test_utf8_only_predicate_high_selectivity_switches_to_one_tile():
     """`s != 'w'` over a large batch selects almost every row: its first call
     runs the sub-tile kernel (no hint yet), the next the one-tile kernel with
-    the LDS-image gather (exec.cpp: high_sel). Both against the oracle, with
+    the LDS-image gather (exec_plan.cpp: high_sel). Both against the oracle, with
     nulls in the Utf8 column and a nullable numeric projection."""
     import torch
     from datafusion_amd import _abi

@@ -1,4 +1,4 @@
-"""GPU parity of the low-selectivity form of numeric predicates (exec.cpp
+"""GPU parity of the low-selectivity form of numeric predicates (exec_plan.cpp
 kLowSel, jit_kernels.cpp "M sub-tiles"): M sub-tiles share one scan + look-back, the
 predicate pass keeps only selection ballots, and the output pass reloads the
 columns the outputs read for the selected rows -- one lane per row while a

@@ -1,7 +1,7 @@
 """Query compiler on the CPU: the kernel source dfmi_filter_project would
 launch is generated for many expression shapes and compiled with hipRTC for
 gfx950 (no device needed), through the library's internal test hook
-dfmi_internal_jit_check (exec.cpp). The GPU suite then runs the same code
+dfmi_internal_jit_check (exec_plan.cpp). The GPU suite then runs the same code
 against the oracle; this suite catches generator / skeleton breakage here."""
 import ctypes as C
 import random
@@ -224,7 +224,7 @@ def test_cast_and_is_null_kernels_compile():
 
 @pytest.mark.parametrize("m", [2, 8])
 def test_numeric_subtile_kernel_compiles(m, monkeypatch):
-    """The low-selectivity form of a numeric predicate (exec.cpp kLowSel:
+    """The low-selectivity form of a numeric predicate (exec_plan.cpp kLowSel:
     sub-tiles sharing one look-back, output pass reloading the selected rows'
     columns), forced through the diagnostic knob; nullable inputs, a
     fallible projection and a Q6-style 5-term predicate."""

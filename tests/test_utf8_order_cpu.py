@@ -107,7 +107,7 @@ def test_kernels_compile_for_gfx950(shape):
 @pytest.mark.parametrize("form,bit", [("one_tile", 0x20000000), ("coalesced_batches", 0x40000000)])
 def test_other_kernel_forms_compile(form, bit):
     """The hook's internal flag bits: the one-tile kernel a Utf8-only predicate switches to once it
-    selected most of a large batch (exec.cpp high_sel), and the coalesced-batches form."""
+    selected most of a large batch (exec_plan.cpp high_sel), and the coalesced-batches form."""
     default = jit_check(S, range_pred(), [Column(0), Column(2)], BOTH)[3]
     rc, code, msg, src = jit_check(S, range_pred(), [Column(0), Column(2)], BOTH | bit, compile_=True)
     assert rc > 0, msg

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of the numeric sub-tile kernel (exec.cpp kLowSel / jit_kernels.cpp "M
+# A/B of the numeric sub-tile kernel (exec_plan.cpp kLowSel / jit_kernels.cpp "M
 # sub-tiles") on the low-selectivity lines: C2 at s = 1% and C4, forced per
 # variant with the diagnostic knob (DFMI_DIAG=1 DFMI_NUMERIC_SUBTILES=M; M=1:
 # the one-tile kernel, the adaptive choice disabled with DFMI_NUMERIC_SUBTILES=1),

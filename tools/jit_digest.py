@@ -301,7 +301,7 @@ def aggregates():
             aggs("boolean extremes grouped key %d%s" % (key, tag), tm.S, p, fns, fl, key=Column(key))
 
 
-# every diagnostic knob the plan builder reads (exec.cpp build_plan_impl), at
+# every diagnostic knob the plan builder reads (exec_plan.cpp apply_diag_knobs), at
 # non-default values, each over the base shapes below
 KNOBS = [
     {"DFMI_ROWS_PER_THREAD": 4}, {"DFMI_BLOCK": 256}, {"DFMI_WAVES_PER_EU": 4}, {"DFMI_LOOKBACK_R": 2},
