@@ -73,7 +73,8 @@ HashDev& hashdev(dfmi_context* ctx, dfmi_agg_state* st) {
     alloc_table(H->ctl, H->slot, H->t, H->cap, ctx->stream);
     H->acc_cap = 1024;
     H->acc.alloc(H->acc_cap * (size_t)w * 8);
-    HIP_TRY(gb::launch_init(H->records(), H->pattern.as<unsigned long long>(), w, 0, H->acc_cap, ctx->stream));
+    HIP_TRY(gb::launch_init(H->records(), H->pattern.as<unsigned long long>(), w, 0, H->acc_cap, group_grid(agg_diag()),
+                            ctx->stream));
     H->arena_cap = 1 << 16;
     H->arena.alloc(H->arena_cap);
     st->hd = std::move(H);
@@ -88,12 +89,12 @@ void read_hdr(dfmi_context* ctx, HashDev& H) {
 }
 
 // A bigger table (cap x 4), every used slot moved (k_group_rehash).
-void grow_table(dfmi_context* ctx, HashDev& H) {
+void grow_table(dfmi_context* ctx, HashDev& H, int grid) {
     DevBuf ctl, slot;
     gb::Table nt;
     const uint64_t ncap = H.cap * 4;
     alloc_table(ctl, slot, nt, ncap, ctx->stream);
-    HIP_TRY(gb::launch_rehash(H.t, nt, ctx->stream));
+    HIP_TRY(gb::launch_rehash(H.t, nt, grid, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     H.ctl = std::move(ctl);  // (the old table goes with the locals)
     H.slot = std::move(slot);
@@ -308,9 +309,10 @@ bool use_buckets(const dfmi_agg_state* st, const HashDev& H, int64_t m, uint64_t
 
 std::atomic<long> g_bucketed_batches{0};  // diagnostics: dfmi_internal_group_bucketed_batches
 std::atomic<long> g_normalize_trips{0};   // diagnostics: dfmi_internal_group_normalize_trips
+std::atomic<long> g_strided_launches{0};  // diagnostics: dfmi_internal_group_strided_launches
 
 void accumulate_bucketed(dfmi_context* ctx, dfmi_agg_state* st, HashDev& H, const std::vector<dfmi::gb::Col>& cols,
-                         int64_t m, uint64_t ng, uint32_t epoch) {
+                         int64_t m, uint64_t ng, uint32_t epoch, int grid) {
     g_bucketed_batches.fetch_add(1);
     const size_t nk = st->keys.size(), n = st->aggs.size();
     const BucketShape sh = bucket_shape(H, ng);
@@ -375,13 +377,14 @@ void accumulate_bucketed(dfmi_context* ctx, dfmi_agg_state* st, HashDev& H, cons
     ba.words = H.words;
     ba.acc = H.records();
     ba.pattern = H.pattern.as<unsigned long long>();
-    HIP_TRY(dfmi::gb::launch_buckets(ra, sa, ba, ctx->stream));
+    HIP_TRY(dfmi::gb::launch_buckets(ra, sa, ba, grid, ctx->stream));
 }
 
 }  // namespace
 
 long bucketed_batches() { return g_bucketed_batches.load(); }
 long normalize_trips() { return g_normalize_trips.load(std::memory_order_relaxed); }
+long strided_launches() { return g_strided_launches.load(std::memory_order_relaxed); }
 
 // Diagnostics (dfmi_internal_group_records): the device records of groups
 // [g0, g0 + ng) copied out as they stand -- nothing normalised, the table left
@@ -539,7 +542,8 @@ void group_batches_hashed(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_prog
         HIP_TRY(hipMemcpyAsync(tab, htab.data(), htab.size(), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));  // (htab is pageable: it must not go before the copy has read it)
         HIP_TRY(dfmi::gb::launch_concat((const unsigned long long*)tab, (const dfmi::gb::ConcatJob*)(tab + sb),
-                                        (int)jobs.size(), (const long long*)(tab + sb + jb), nb, m, ctx->stream));
+                                        (int)jobs.size(), (const long long*)(tab + sb + jb), nb, m, group_grid(diag),
+                                        ctx->stream));
         if (diag.finish_profile) HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     accumulate_hashed(ctx, st, cols, m, diag, t0);
@@ -557,6 +561,7 @@ void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<
     if (m > 0x7fffffffll) throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "GROUP BY batch of 2^31 selected rows or more"};
     const size_t nk = st->keys.size(), n = st->aggs.size();
     hipStream_t stream = ctx->stream;
+    const int grid = group_grid(diag);
     // a Boolean MIN / MAX is an integer extreme over 0 / 1: its bitmap expanded to a
     // UInt8 column, which every pass below (and the host merge) takes as it is
     std::vector<dfmi::gb::Col> cols = evaluated;
@@ -564,7 +569,7 @@ void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<
         dfmi::gb::Col& c = cols[nk + j];
         if (c.type != DFMI_TYPE_BOOLEAN || st->aggs[j]->fn == DFMI_AGG_COUNT) continue;
         uint8_t* u8 = (uint8_t*)H.bufs[HashDev::BoolArg + j].reserve((size_t)(m + 7) / 8 * 8);
-        HIP_TRY(dfmi::gb::launch_bits_to_u8((const uint8_t*)c.values, u8, m, stream));
+        HIP_TRY(dfmi::gb::launch_bits_to_u8((const uint8_t*)c.values, u8, m, grid, stream));
         c.type = DFMI_TYPE_UINT8;
         c.width = 1;
         c.values = u8;
@@ -591,12 +596,12 @@ void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<
         ca.t = H.t;
         ca.limit = H.cap / 2;
         HIP_TRY(hipMemsetAsync(&H.dhdr()->overflow, 0, 8, stream));
-        HIP_TRY(dfmi::gb::launch_claim(ca, stream));
+        HIP_TRY(dfmi::gb::launch_claim(ca, grid, stream));
         read_hdr(ctx, H);
         if (!H.hh.p->overflow) break;
         if (H.cap >= (1ull << 31) || attempt > 16)
             throw Fail{DFMI_ERR_NOT_IMPLEMENTED, "GROUP BY: more than 2^30 groups on one device"};
-        grow_table(ctx, H);
+        grow_table(ctx, H, grid);
     }
     const uint64_t ng = H.hh.p->ngroups, aend = H.hh.p->arena_end;
     const auto t2 = std::chrono::steady_clock::now();
@@ -604,7 +609,8 @@ void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<
         uint64_t want = H.acc_cap;
         while (want < ng) want *= 2;
         H.acc.regrow(ctx->stream, H.acc_cap * (size_t)H.words * 8, want * (size_t)H.words * 8);
-        HIP_TRY(dfmi::gb::launch_init(H.records(), H.pattern.as<unsigned long long>(), H.words, H.acc_cap, want, stream));
+        HIP_TRY(dfmi::gb::launch_init(H.records(), H.pattern.as<unsigned long long>(), H.words, H.acc_cap, want, grid,
+                                      stream));
         H.acc_cap = want;
     }
     if (aend > H.arena_cap) {
@@ -616,14 +622,15 @@ void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<
     // exact-sum digits absorb 2^31 rows between carry normalisations
     if (!H.foff.empty() && H.rows_since_norm + (uint64_t)m > group_norm_rows(diag)) {
         g_normalize_trips.fetch_add(1, std::memory_order_relaxed);
-        HIP_TRY(dfmi::gb::launch_normalize(H.records(), H.words, H.foff.data(), (int)H.foff.size(), H.ngroups, stream));
+        HIP_TRY(dfmi::gb::launch_normalize(H.records(), H.words, H.foff.data(), (int)H.foff.size(), H.ngroups, grid,
+                                           stream));
         H.rows_since_norm = 0;
     }
     HIP_TRY(hipMemsetAsync(&H.dhdr()->collided, 0, 8, stream));
     // (a state with Utf8 MIN / MAX aggregates keeps the rows' group ids for the string passes)
     unsigned* rg = st->sx ? (unsigned*)H.bufs[HashDev::BucketRowGroup].reserve((size_t)m * 4) : nullptr;
     if (use_buckets(st, H, m, ng, diag)) {
-        accumulate_bucketed(ctx, st, H, cols, m, ng, ca.epoch);
+        accumulate_bucketed(ctx, st, H, cols, m, ng, ca.epoch, grid);
     } else {
         dfmi::gb::AccArgs aa{};
         for (size_t p = 0; p < nk; ++p) aa.k[p] = cols[p];
@@ -645,13 +652,13 @@ void accumulate_hashed(dfmi_context* ctx, dfmi_agg_state* st, const std::vector<
         aa.hdr = H.dhdr();
         aa.coll_rows = H.coll.as<int32_t>();
         aa.rg = rg;
-        HIP_TRY(dfmi::gb::launch_accumulate(aa, stream));
+        HIP_TRY(dfmi::gb::launch_accumulate(aa, grid, stream));
     }
     // Utf8 MIN / MAX: the strings of the rows added on the device (the listed rows' go with the host merge below)
     // (the records have counted the batch: a failure of the string passes fails the query)
     H.ngroups = ng;
     try {
-        strext_batch(ctx, st, cols.data() + nk, rg, m, ng);
+        strext_batch(ctx, st, cols.data() + nk, rg, m, ng, diag);
     } catch (const Fail& f) {
         st->failed = true;
         set_err(&st->failure, f.code, f.msg);
@@ -696,7 +703,7 @@ void parallel_ranges(uint64_t n, uint64_t grain, const F& fn) {
 
 // Every group's record finished on the device (k_group_round) into the
 // DrainRounded buffer: word 0 and four words per aggregate.
-const unsigned long long* round_records(dfmi_context* ctx, const dfmi_agg_state* st, HashDev& H) {
+const unsigned long long* round_records(dfmi_context* ctx, const dfmi_agg_state* st, HashDev& H, int grid) {
     const size_t n = st->aggs.size();
     dfmi::gb::RoundArgs ra{};
     ra.acc = H.records();
@@ -712,7 +719,7 @@ const unsigned long long* round_records(dfmi_context* ctx, const dfmi_agg_state*
     }
     ra.ngroups = H.ngroups;
     ra.out = (unsigned long long*)H.bufs[HashDev::DrainRounded].reserve(H.ngroups * (1 + 4 * n) * 8);
-    HIP_TRY(dfmi::gb::launch_round(ra, ctx->stream));
+    HIP_TRY(dfmi::gb::launch_round(ra, grid, ctx->stream));
     return ra.out;
 }
 
@@ -722,7 +729,7 @@ const unsigned long long* round_records(dfmi_context* ctx, const dfmi_agg_state*
 // finish), every record finished on the device first (k_group_round: the
 // compact records without their exact-sum digits cross PCIe) and the table
 // kept as it is, so that more batches can still merge into it.
-void read_table(dfmi_context* ctx, dfmi_agg_state* st, FlatGroups& f, bool rounded = false) {
+void read_table(dfmi_context* ctx, dfmi_agg_state* st, FlatGroups& f, const AggDiag& diag, bool rounded = false) {
     HashDev& H = *st->hd;
     const size_t nk = st->keys.size(), n = st->aggs.size();
     const uint64_t ng = H.ngroups;
@@ -735,12 +742,12 @@ void read_table(dfmi_context* ctx, dfmi_agg_state* st, FlatGroups& f, bool round
     if (rounded) {
         for (size_t j = 0; j < n; ++j) f.off[j] = 1 + 4 * (int)j;
         f.words = 1 + 4 * (int)n;
-        src = round_records(ctx, st, H);
+        src = round_records(ctx, st, H, group_grid(diag));
     }
     unsigned* dnull = (unsigned*)H.bufs[HashDev::DrainNull].reserve(ng * 4);
     unsigned long long* dkw = (unsigned long long*)H.bufs[HashDev::DrainKeyWords].reserve(ng * nk * 8);
     unsigned* dklen = (unsigned*)H.bufs[HashDev::DrainKeyLens].reserve(ng * nk * 4);
-    HIP_TRY(dfmi::gb::launch_compact(H.t, (int)nk, dnull, dkw, dklen, ctx->stream));
+    HIP_TRY(dfmi::gb::launch_compact(H.t, (int)nk, dnull, dkw, dklen, group_grid(diag), ctx->stream));
     f.knull.resize(ng);
     f.klen.resize(ng * nk);
     f.kw.resize(ng * nk);
@@ -754,8 +761,8 @@ void read_table(dfmi_context* ctx, dfmi_agg_state* st, FlatGroups& f, bool round
     if (H.hh.p->arena_end) HIP_TRY(hipMemcpy(f.arena.data(), H.arena.as<uint8_t>(), H.hh.p->arena_end, hipMemcpyDeviceToHost));
     strext_read(ctx, st, f, ng);
     if (rounded) return;
-    reset_table(ctx, H);  // for the next batch
-    strext_reset(ctx, st);
+    reset_table(ctx, H, diag);  // for the next batch
+    strext_reset(ctx, st, diag);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
 }
 
@@ -973,10 +980,11 @@ std::unique_ptr<FlatGroups> take_flat(dfmi_agg_state* st) {
 }  // namespace
 
 // An empty table of the same size (enqueued on the stream).
-void reset_table(dfmi_context* ctx, HashDev& H) {
+void reset_table(dfmi_context* ctx, HashDev& H, const AggDiag& diag) {
     HIP_TRY(hipMemsetAsync(H.t.ctl, 0, H.cap * 8, ctx->stream));
     HIP_TRY(hipMemsetAsync(H.hdr.p, 0, sizeof(dfmi::gb::Hdr), ctx->stream));
-    HIP_TRY(dfmi::gb::launch_init(H.records(), H.pattern.as<unsigned long long>(), H.words, 0, H.ngroups, ctx->stream));
+    HIP_TRY(dfmi::gb::launch_init(H.records(), H.pattern.as<unsigned long long>(), H.words, 0, H.ngroups, group_grid(diag),
+                                  ctx->stream));
     H.ngroups = 0;
     H.rows_since_norm = 0;
 }
@@ -997,7 +1005,7 @@ void drain_hashed(dfmi_context* ctx, dfmi_agg_state* st) {
     unflatten(st);
     if (!st->hd || !st->hd->ngroups) return;
     std::unique_ptr<FlatGroups> f = take_flat(st);
-    read_table(ctx, st, *f);
+    read_table(ctx, st, *f, agg_diag());
     materialize_flat(st, *f);
     st->spare_flat = std::move(f);
 }
@@ -1015,7 +1023,7 @@ bool finish_flat(dfmi_context* ctx, dfmi_agg_state* st, const AggDiag& diag) {
         if (!st->hd || !st->hd->ngroups) return false;
         std::unique_ptr<FlatGroups> f = take_flat(st);
         const auto t0 = std::chrono::steady_clock::now();
-        read_table(ctx, st, *f, !diag.host_finish);
+        read_table(ctx, st, *f, diag, !diag.host_finish);
         const auto t1 = std::chrono::steady_clock::now();
         sort_flat(st, *f);
         if (diag.finish_profile)
@@ -1056,17 +1064,18 @@ bool finish_device(dfmi_context* ctx, dfmi_agg_state* st, const AggDiag& diag, i
     if (st->flat) st->spare_flat = std::move(st->flat);
     const size_t n = st->aggs.size();
     hipStream_t stream = ctx->stream;
+    const int grid = group_grid(diag);
     dfmi::gb::EmitArgs ea{};
     for (size_t j = 0; j < n; ++j) {
         ea.fn[j] = st->aggs[j]->fn;
         ea.atype[j] = st->aggs[j]->arg.type;
         ea.rtype[j] = st->aggs[j]->ret_type;
     }
-    ea.rec = round_records(ctx, st, H);
+    ea.rec = round_records(ctx, st, H, grid);
     unsigned* dnull = (unsigned*)H.bufs[HashDev::DrainNull].reserve(ng * 4);
     unsigned long long* dkw = (unsigned long long*)H.bufs[HashDev::DrainKeyWords].reserve(ng * 8);
     unsigned* dklen = (unsigned*)H.bufs[HashDev::DrainKeyLens].reserve(ng * 4);
-    HIP_TRY(dfmi::gb::launch_compact(H.t, 1, dnull, dkw, dklen, stream));
+    HIP_TRY(dfmi::gb::launch_compact(H.t, 1, dnull, dkw, dklen, grid, stream));
     ea.knull = dnull;
     ea.kw = dkw;
     ea.ngroups = ng;
@@ -1080,9 +1089,9 @@ bool finish_device(dfmi_context* ctx, dfmi_agg_state* st, const AggDiag& diag, i
     auto* sv2 = (unsigned*)H.bufs[HashDev::EmitSortVals2].reserve(ng * 4);
     auto* null_at = (unsigned*)H.bufs[HashDev::EmitNullAt].reserve(8);
     size_t tb = 0;
-    HIP_TRY(dfmi::gb::launch_emit(ea, sk, sk2, sv, sv2, null_at, nullptr, &tb, stream));
+    HIP_TRY(dfmi::gb::launch_emit(ea, sk, sk2, sv, sv2, null_at, nullptr, &tb, grid, stream));
     void* tmp = H.bufs[HashDev::EmitTemp].reserve(tb);
-    HIP_TRY(dfmi::gb::launch_emit(ea, sk, sk2, sv, sv2, null_at, tmp, &tb, stream));
+    HIP_TRY(dfmi::gb::launch_emit(ea, sk, sk2, sv, sv2, null_at, tmp, &tb, grid, stream));
     HIP_TRY(hipMemcpyAsync(keys, ea.keys, ng * sizeof(dfmi_agg_value), hipMemcpyDeviceToHost, stream));
     if (n) HIP_TRY(hipMemcpyAsync(values, ea.values, ng * n * sizeof(dfmi_agg_value), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -1162,3 +1171,6 @@ void emit_key_bytes_flat(const FlatGroups& f, int part, int32_t* offsets, int64_
 
 }  // namespace agg
 }  // namespace dfmi
+
+// groupby.h "Diagnostic grid cap": a kernel launch took more than one trip of its grid.
+void dfmi::gb::count_strided_launch() { dfmi::agg::g_strided_launches.fetch_add(1, std::memory_order_relaxed); }

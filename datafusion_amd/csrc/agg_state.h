@@ -156,6 +156,7 @@ struct AggDiag {
     const char* rows_per_thread = nullptr;  // DFMI_ROWS_PER_THREAD
     const char* proj_dense = nullptr;       // DFMI_PROJ_DENSE
     const char* group_norm_rows = nullptr;  // DFMI_GROUP_NORM_ROWS
+    const char* group_grid = nullptr;       // DFMI_GROUP_GRID
 };
 
 // Rows a grouped state's exact-sum digits absorb between two carry
@@ -175,6 +176,7 @@ inline AggDiag agg_diag() {
     d.rows_per_thread = getenv("DFMI_ROWS_PER_THREAD");
     d.proj_dense = getenv("DFMI_PROJ_DENSE");
     d.group_norm_rows = getenv("DFMI_GROUP_NORM_ROWS");
+    d.group_grid = getenv("DFMI_GROUP_GRID");
     return d;
 }
 
@@ -185,6 +187,16 @@ inline uint64_t group_norm_rows(const AggDiag& diag) {
     if (!diag.group_norm_rows) return kGroupNormRows;
     const long long v = atoll(diag.group_norm_rows);
     return v < 0 ? 0 : std::min<uint64_t>((uint64_t)v, kGroupNormRows);
+}
+
+// DFMI_GROUP_GRID (diagnostics): the workgroups of every launch of groupby.hip
+// and str_extreme.hip lowered to at most its value (groupby.h "Diagnostic grid
+// cap"; each launch clamps it to [1, its own cap] -- the knob never raises a
+// grid). 0: unset, every launch's own grid.
+inline int group_grid(const AggDiag& diag) {
+    if (!diag.group_grid) return 0;
+    const long long v = atoll(diag.group_grid);
+    return v < 1 ? 1 : (int)std::min<long long>(v, 1 << 30);
 }
 
 // The sticky failure of a state: a batch has failed the query.
@@ -222,7 +234,7 @@ void group_batch_hashed(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_progra
 // first failing batch (the state is failed and the error thrown).
 void group_batches_hashed(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* ins,
                           int32_t nb, uint32_t flags, const AggDiag& diag, int32_t* failed);
-void reset_table(dfmi_context* ctx, HashDev& H);
+void reset_table(dfmi_context* ctx, HashDev& H, const AggDiag& diag);
 void unflatten(dfmi_agg_state* st);
 void drain_hashed(dfmi_context* ctx, dfmi_agg_state* st);
 bool finish_flat(dfmi_context* ctx, dfmi_agg_state* st, const AggDiag& diag);
@@ -234,6 +246,7 @@ void emit_key_bytes_flat(const FlatGroups& f, int part, int32_t* offsets, int64_
                          int64_t data_capacity, int64_t* data_length);
 long bucketed_batches();
 long normalize_trips();
+long strided_launches();
 void read_records(dfmi_context* ctx, dfmi_agg_state* st, uint64_t g0, uint64_t ng, uint64_t* out, int64_t* info);
 
 // ---- agg_strext.cpp: the Utf8 MIN / MAX side structure's driver
@@ -241,10 +254,11 @@ void strext_create(dfmi_context* ctx, dfmi_agg_state* st);  // st->sx when the s
 // one batch's m evaluated rows: cols[j] the argument column of aggregate j (only the Utf8 extremes' are read),
 // rg the rows' dense group ids (null: one group), ngroups the groups the device holds
 void strext_batch(dfmi_context* ctx, dfmi_agg_state* st, const dfmi::gb::Col* arg_cols, const unsigned* rg, int64_t m,
-                  uint64_t ngroups);
+                  uint64_t ngroups, const AggDiag& diag);
 void strext_batch_ungrouped(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* in,
-                            uint32_t flags);
-void strext_reset(dfmi_context* ctx, dfmi_agg_state* st);  // the device side emptied (the last finish's values stay)
+                            uint32_t flags, const AggDiag& diag);
+// the device side emptied (the last finish's values stay)
+void strext_reset(dfmi_context* ctx, dfmi_agg_state* st, const AggDiag& diag);
 // the first ng groups' winners and the arena on the host (f.sx_ent, f.sx_arena)
 void strext_read(dfmi_context* ctx, dfmi_agg_state* st, FlatGroups& f, uint64_t ng);
 void strext_finish_ungrouped(dfmi_context* ctx, dfmi_agg_state* st, dfmi_agg_value* out);

@@ -24,7 +24,7 @@ namespace {
 constexpr uint64_t kArena0 = 1 << 16;
 
 // The side arrays hold (initialised) at least `ng` groups.
-void ensure_groups(dfmi_context* ctx, StrExt& S, uint64_t ng) {
+void ensure_groups(dfmi_context* ctx, StrExt& S, uint64_t ng, int grid) {
     if (ng <= S.gcap) return;
     uint64_t want = std::max<uint64_t>(S.gcap, 1);
     while (want < ng) want *= 2;
@@ -33,7 +33,7 @@ void ensure_groups(dfmi_context* ctx, StrExt& S, uint64_t ng) {
         o.best.regrow(ctx->stream, S.gcap * 4, want * 4);
         o.ent.regrow(ctx->stream, S.gcap * sizeof(sx::Ent), want * sizeof(sx::Ent));
         HIP_TRY(sx::launch_init(o.pref.as<unsigned long long>(), o.best.as<unsigned>(), o.ent.as<sx::Ent>(), o.is_min, S.gcap,
-                                want, ctx->stream));
+                                want, grid, ctx->stream));
     }
     S.gcap = want;
 }
@@ -60,7 +60,7 @@ sx::Hdr read_hdr(dfmi_context* ctx, StrExt& S) {
 // compacted straight into a fresh one, a power of two in which live + need
 // fill at most half -- so the arena holds at most four times the winners'
 // bytes plus what one batch keeps, and shrinks again when they do.
-void ensure_arena(dfmi_context* ctx, StrExt& S, uint64_t ng, uint64_t need) {
+void ensure_arena(dfmi_context* ctx, StrExt& S, uint64_t ng, uint64_t need, int grid) {
     if (S.arena_end + need <= S.arena_cap) return;
     uint64_t cap = kArena0;
     while (cap < 2 * (S.live + need)) cap *= 2;
@@ -70,7 +70,7 @@ void ensure_arena(dfmi_context* ctx, StrExt& S, uint64_t ng, uint64_t need) {
     // all extremes share the arena: each compacts its strings behind the last one's
     for (StrExt::One& o : S.x)
         HIP_TRY(sx::launch_compact(o.ent.as<sx::Ent>(), std::min(ng, S.gcap), S.arena.as<unsigned char>(),
-                                   fresh.as<unsigned char>(), cap, S.hdr.as<sx::Hdr>(), ctx->stream));
+                                   fresh.as<unsigned char>(), cap, S.hdr.as<sx::Hdr>(), grid, ctx->stream));
     const sx::Hdr h = read_hdr(ctx, S);
     if (h.arena_end != S.live) throw Fail{DFMI_ERR_DEVICE, "Utf8 MIN / MAX: the string arena's live bytes do not add up"};
     S.arena = std::move(fresh);  // (the old arena goes with the local)
@@ -95,7 +95,7 @@ void strext_create(dfmi_context* ctx, dfmi_agg_state* st) {
     S->arena.alloc(kArena0);
     S->arena_cap = kArena0;
     S->one.assign(st->aggs.size(), StrVal{});
-    ensure_groups(ctx, *S, st->grouped ? 1024 : 1);
+    ensure_groups(ctx, *S, st->grouped ? 1024 : 1, group_grid(agg_diag()));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     st->sx = std::move(S);
 }
@@ -103,7 +103,7 @@ void strext_create(dfmi_context* ctx, dfmi_agg_state* st) {
 // The device side emptied: no group holds a winner (a reset, or a drain of the
 // table whose group ids these arrays follow). What the last finish produced
 // (StrExt::one, finished) is the caller's to keep or drop.
-void strext_reset(dfmi_context* ctx, dfmi_agg_state* st) {
+void strext_reset(dfmi_context* ctx, dfmi_agg_state* st, const AggDiag& diag) {
     if (!st->sx) return;
     StrExt& S = *st->sx;
     if (S.arena_cap > kArena0) {  // (a large batch's arena is not kept for the state's lifetime)
@@ -113,16 +113,17 @@ void strext_reset(dfmi_context* ctx, dfmi_agg_state* st) {
     }
     for (StrExt::One& o : S.x)
         HIP_TRY(sx::launch_init(o.pref.as<unsigned long long>(), o.best.as<unsigned>(), o.ent.as<sx::Ent>(), o.is_min, 0, S.gcap,
-                                ctx->stream));
+                                group_grid(diag), ctx->stream));
     HIP_TRY(hipMemsetAsync(S.hdr.p, 0, sizeof(sx::Hdr), ctx->stream));
     S.arena_end = S.live = 0;
 }
 
 void strext_batch(dfmi_context* ctx, dfmi_agg_state* st, const dfmi::gb::Col* arg_cols, const unsigned* rg, int64_t m,
-                  uint64_t ngroups) {
+                  uint64_t ngroups, const AggDiag& diag) {
     if (!st->sx || m <= 0 || !ngroups) return;
     StrExt& S = *st->sx;
-    ensure_groups(ctx, S, ngroups);
+    const int grid = group_grid(diag);
+    ensure_groups(ctx, S, ngroups, grid);
     auto args = [&](const StrExt::One& o) {
         const dfmi::gb::Col& c = arg_cols[o.agg];
         sx::Args a{};
@@ -143,9 +144,9 @@ void strext_batch(dfmi_context* ctx, dfmi_agg_state* st, const dfmi::gb::Col* ar
     };
     // the batch's winners found and their bytes measured; then exactly that much room; then kept
     HIP_TRY(hipMemsetAsync(&S.hdr.as<sx::Hdr>()->need, 0, 8, ctx->stream));
-    for (const StrExt::One& o : S.x) HIP_TRY(sx::launch_find(args(o), ctx->stream));
-    ensure_arena(ctx, S, ngroups, read_hdr(ctx, S).need);
-    for (const StrExt::One& o : S.x) HIP_TRY(sx::launch_keep(args(o), ctx->stream));
+    for (const StrExt::One& o : S.x) HIP_TRY(sx::launch_find(args(o), grid, ctx->stream));
+    ensure_arena(ctx, S, ngroups, read_hdr(ctx, S).need, grid);
+    for (const StrExt::One& o : S.x) HIP_TRY(sx::launch_keep(args(o), grid, ctx->stream));
     const sx::Hdr h = read_hdr(ctx, S);
     S.arena_end = h.arena_end;
     S.live = h.live;
@@ -157,7 +158,7 @@ void strext_batch(dfmi_context* ctx, dfmi_agg_state* st, const dfmi::gb::Col* ar
 // Projection pass with the same predicate (a pass-through without one), then
 // the passes with every row in group 0.
 void strext_batch_ungrouped(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_program* pred, const dfmi_batch* in,
-                            uint32_t flags) {
+                            uint32_t flags, const AggDiag& diag) {
     if (!st->sx || in->num_rows <= 0) return;
     StrExt& S = *st->sx;
     const size_t nx = S.x.size();
@@ -201,7 +202,7 @@ void strext_batch_ungrouped(dfmi_context* ctx, dfmi_agg_state* st, const dfmi_pr
             d.validity = c.null_count > 0 ? c.validity : nullptr;
         }
     }
-    strext_batch(ctx, st, cols.data(), nullptr, outs[0].length, 1);
+    strext_batch(ctx, st, cols.data(), nullptr, outs[0].length, 1, diag);
 }
 
 void strext_read(dfmi_context* ctx, dfmi_agg_state* st, FlatGroups& f, uint64_t ng) {

@@ -397,8 +397,9 @@ extern "C" int32_t dfmi_agg_state_reset(dfmi_context* ctx, dfmi_agg_state* st, d
         HIP_TRY(hipSetDevice(ctx->device));
         if (st->acc.p)
             HIP_TRY(hipMemcpyAsync(st->acc.p, st->init.data(), st->acc_words * 8, hipMemcpyHostToDevice, ctx->stream));
-        if (st->hd) reset_table(ctx, *st->hd);
-        strext_reset(ctx, st);
+        const AggDiag diag = agg_diag();
+        if (st->hd) reset_table(ctx, *st->hd, diag);
+        strext_reset(ctx, st, diag);
         if (st->sx) {  // (and no finish to ask dfmi_agg_state_value_bytes about)
             st->sx->finished = false;
             st->sx->one.assign(st->aggs.size(), StrVal{});
@@ -559,7 +560,7 @@ extern "C" int32_t dfmi_aggregate_batch(dfmi_context* ctx, dfmi_agg_state* st, c
         // (the records have counted the batch: a failure here fails the query like the kernel's own)
         if (!st->grouped && st->sx && n > 0) {
             try {
-                strext_batch_ungrouped(ctx, st, pred, in, flags);
+                strext_batch_ungrouped(ctx, st, pred, in, flags, diag);
             } catch (const Fail& f) {
                 st->failed = true;
                 set_err(&st->failure, f.code, f.msg);
@@ -655,6 +656,9 @@ int32_t dfmi_agg_state_show_merged(dfmi_agg_state* st, const void* const* partia
 extern "C" long dfmi_internal_group_bucketed_batches() { return bucketed_batches(); }
 // Diagnostics: times the exact-sum digits' normalisation threshold tripped (accumulate_hashed) in this process.
 extern "C" long dfmi_internal_group_normalize_trips() { return normalize_trips(); }
+// Diagnostics: kernel launches of groupby.hip / str_extreme.hip whose work exceeded one trip of their grid
+// (groupby.h "Diagnostic grid cap") in this process.
+extern "C" long dfmi_internal_group_strided_launches() { return strided_launches(); }
 // Diagnostics: the hash table's device records of groups [g0, g0 + ng), by group id, as they stand (a carry pass
 // preserves an exact sum's value, so only the digits themselves show whether it ran over a record): out
 // [ng][words] (null: only info), info [3 + 15]: words, groups, float SUMs, their digit offsets.

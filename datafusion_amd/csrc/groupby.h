@@ -35,6 +35,18 @@ namespace gb {
 constexpr int kMaxKeys = 4;   // GROUP BY key expressions
 constexpr int kMaxAggs = 15;  // aggregates of one grouped state
 
+// Diagnostic grid cap. Every kernel here and in str_extreme.hip but
+// k_group_scan and k_group_bucket (one block per bucket, per bucket and split)
+// is a grid-stride or tile-stride loop over a capped grid, and every launch_*
+// function takes `grid`: 0 -- the launch's own cap, the shipped grids; else
+// (DFMI_DIAG=1 DFMI_GROUP_GRID, agg_state.h group_grid) at most that many
+// workgroups, never more than the launch's own cap, so that a test's few
+// thousand rows take the later trips that production takes past a few million.
+// A kernel launch whose work exceeds one trip of the grid it runs -- items >
+// blocks x block size; the rank and scatter passes: rows > blocks x their
+// 4,096-row tile -- counts itself (dfmi_internal_group_strided_launches).
+void count_strided_launch();  // agg_hash.cpp
+
 // One key part or aggregate argument: a compacted output column (or a
 // passed-through input column) of the fused pass.
 struct Col {
@@ -195,7 +207,7 @@ struct BucketArgs {
     const unsigned long long* pattern;  // one zero-state record
 };
 
-hipError_t launch_buckets(const RankArgs& r, ScatterArgs s, BucketArgs b, hipStream_t stream);
+hipError_t launch_buckets(const RankArgs& r, ScatterArgs s, BucketArgs b, int grid, hipStream_t stream);
 
 // The finish of every group on the device (k_group_round): per group a
 // compact record [rows, then per aggregate nulls, flags, key, aux] -- the
@@ -240,7 +252,7 @@ struct EmitArgs {
 // temporary storage `tmp` of `tmp_bytes`; tmp == nullptr: *tmp_bytes is set),
 // the null group's position, the emission.
 hipError_t launch_emit(EmitArgs a, unsigned long long* sk, unsigned long long* sk2, unsigned* sv, unsigned* sv2,
-                       unsigned* null_at, void* tmp, size_t* tmp_bytes, hipStream_t stream);
+                       unsigned* null_at, void* tmp, size_t* tmp_bytes, int grid, hipStream_t stream);
 
 // Coalesced batches (agg_batches.cpp): the evaluation pass leaves every
 // output column in per-batch segments; one pack job per buffer (a column's
@@ -257,24 +269,24 @@ struct ConcatJob {
     int pad;
 };
 hipError_t launch_concat(const unsigned long long* srcs, const ConcatJob* jobs, int njobs, const long long* prefix,
-                         int nb, long long m, hipStream_t stream);
+                         int nb, long long m, int grid, hipStream_t stream);
 
 // The m bits of a Boolean bitmap as m UInt8 values 0 / 1: the argument of a
 // Boolean MIN / MAX, which the passes above then take as a UInt8 column.
 // `dst` holds (m + 7) / 8 * 8 bytes, 8-byte aligned.
-hipError_t launch_bits_to_u8(const unsigned char* bits, unsigned char* dst, long long m, hipStream_t stream);
+hipError_t launch_bits_to_u8(const unsigned char* bits, unsigned char* dst, long long m, int grid, hipStream_t stream);
 
 // groupby.hip: launches on `stream` (asynchronous)
-hipError_t launch_claim(const ClaimArgs& a, hipStream_t stream);
-hipError_t launch_accumulate(const AccArgs& a, hipStream_t stream);
-hipError_t launch_rehash(const Table& from, const Table& to, hipStream_t stream);
-hipError_t launch_compact(const Table& t, int nkeys, unsigned* knull, unsigned long long* kw, unsigned* klen,
+hipError_t launch_claim(const ClaimArgs& a, int grid, hipStream_t stream);
+hipError_t launch_accumulate(const AccArgs& a, int grid, hipStream_t stream);
+hipError_t launch_rehash(const Table& from, const Table& to, int grid, hipStream_t stream);
+hipError_t launch_compact(const Table& t, int nkeys, unsigned* knull, unsigned long long* kw, unsigned* klen, int grid,
                           hipStream_t stream);
 hipError_t launch_init(unsigned long long* acc, const unsigned long long* pattern, int words, unsigned long long g0,
-                       unsigned long long g1, hipStream_t stream);
-hipError_t launch_round(const RoundArgs& a, hipStream_t stream);
+                       unsigned long long g1, int grid, hipStream_t stream);
+hipError_t launch_round(const RoundArgs& a, int grid, hipStream_t stream);
 hipError_t launch_normalize(unsigned long long* acc, int words, const int* foff, int nf, unsigned long long ngroups,
-                            hipStream_t stream);
+                            int grid, hipStream_t stream);
 
 }  // namespace gb
 }  // namespace dfmi

@@ -1251,13 +1251,20 @@ __global__ __launch_bounds__(256) void k_group_bits_to_u8(const u8* bits, u64* d
     }
 }
 
-static int grid_for(long long items, int per_block = 256, int cap = 8192) {
+// Workgroups for `items`: one per `per_block` items, at most `cap` -- and at
+// most `diag` when that is set (DFMI_GROUP_GRID, groupby.h "Diagnostic grid
+// cap": it only lowers a grid). A launch that needs more than one trip of its
+// grid counts itself.
+static int grid_for(long long items, int diag, int per_block = 256, int cap = 8192) {
+    if (diag > 0 && diag < cap) cap = diag;
     long long g = (items + per_block - 1) / per_block;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+    const int blocks = (int)(g < 1 ? 1 : (g > cap ? cap : g));
+    if (items > (long long)blocks * per_block) count_strided_launch();
+    return blocks;
 }
 
-hipError_t launch_claim(const ClaimArgs& a, hipStream_t st) {
-    const dim3 g(grid_for(a.m)), b(256);
+hipError_t launch_claim(const ClaimArgs& a, int grid, hipStream_t st) {
+    const dim3 g(grid_for(a.m, grid)), b(256);
     switch (a.nkeys) {
         case 1: hipLaunchKernelGGL(k_group_claim<1>, g, b, 0, st, a); break;
         case 2: hipLaunchKernelGGL(k_group_claim<2>, g, b, 0, st, a); break;
@@ -1268,8 +1275,8 @@ hipError_t launch_claim(const ClaimArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_accumulate(const AccArgs& a, hipStream_t st) {
-    const dim3 g(grid_for(a.m)), b(256);
+hipError_t launch_accumulate(const AccArgs& a, int grid, hipStream_t st) {
+    const dim3 g(grid_for(a.m, grid)), b(256);
     switch (a.nkeys) {
         case 1: hipLaunchKernelGGL(k_group_accumulate<1>, g, b, 0, st, a); break;
         case 2: hipLaunchKernelGGL(k_group_accumulate<2>, g, b, 0, st, a); break;
@@ -1281,42 +1288,52 @@ hipError_t launch_accumulate(const AccArgs& a, hipStream_t st) {
 }
 
 hipError_t launch_concat(const unsigned long long* srcs, const ConcatJob* jobs, int njobs, const long long* prefix,
-                         int nb, long long m, hipStream_t st) {
+                         int nb, long long m, int grid, hipStream_t st) {
     if (nb < 1 || nb > kConcatMaxBatches || njobs < 1) return hipErrorInvalidValue;
     if (m <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_group_concat, dim3(grid_for(m, 256, 2048), njobs), dim3(256), 0, st, srcs, jobs, prefix, nb, m);
+    hipLaunchKernelGGL(k_group_concat, dim3(grid_for(m, grid, 256, 2048), njobs), dim3(256), 0, st, srcs, jobs, prefix, nb,
+                       m);
     return hipGetLastError();
 }
 
-hipError_t launch_bits_to_u8(const unsigned char* bits, unsigned char* dst, long long m, hipStream_t st) {
+hipError_t launch_bits_to_u8(const unsigned char* bits, unsigned char* dst, long long m, int grid, hipStream_t st) {
     if (m <= 0) return hipSuccess;
     const long long nbytes = (m + 7) / 8;
-    hipLaunchKernelGGL(k_group_bits_to_u8, dim3(grid_for(nbytes, 256, 2048)), dim3(256), 0, st, bits, (u64*)dst, nbytes);
+    hipLaunchKernelGGL(k_group_bits_to_u8, dim3(grid_for(nbytes, grid, 256, 2048)), dim3(256), 0, st, bits, (u64*)dst,
+                       nbytes);
     return hipGetLastError();
 }
 
-hipError_t launch_rehash(const Table& o, const Table& n, hipStream_t st) {
-    hipLaunchKernelGGL(k_group_rehash, dim3(grid_for((long long)o.mask + 1)), dim3(256), 0, st, o, n);
+hipError_t launch_rehash(const Table& o, const Table& n, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(k_group_rehash, dim3(grid_for((long long)o.mask + 1, grid)), dim3(256), 0, st, o, n);
     return hipGetLastError();
 }
 
-hipError_t launch_compact(const Table& t, int nkeys, unsigned* knull, unsigned long long* kw, unsigned* klen,
+hipError_t launch_compact(const Table& t, int nkeys, unsigned* knull, unsigned long long* kw, unsigned* klen, int grid,
                           hipStream_t st) {
-    hipLaunchKernelGGL(k_group_compact, dim3(grid_for((long long)t.mask + 1)), dim3(256), 0, st, t, nkeys, knull, kw,
-                       klen);
+    hipLaunchKernelGGL(k_group_compact, dim3(grid_for((long long)t.mask + 1, grid)), dim3(256), 0, st, t, nkeys, knull,
+                       kw, klen);
     return hipGetLastError();
 }
 
-hipError_t launch_init(u64* acc, const u64* pattern, int words, u64 g0, u64 g1, hipStream_t st) {
+hipError_t launch_init(u64* acc, const u64* pattern, int words, u64 g0, u64 g1, int grid, hipStream_t st) {
     if (g1 <= g0) return hipSuccess;
-    hipLaunchKernelGGL(k_group_init, dim3(grid_for((long long)((g1 - g0) * words))), dim3(256), 0, st, acc, pattern,
+    hipLaunchKernelGGL(k_group_init, dim3(grid_for((long long)((g1 - g0) * words), grid)), dim3(256), 0, st, acc, pattern,
                        words, g0, g1);
     return hipGetLastError();
 }
 
-hipError_t launch_buckets(const RankArgs& r, ScatterArgs s, BucketArgs b, hipStream_t st) {
-    const dim3 g(kBucketBlocks), blk(256);
+hipError_t launch_buckets(const RankArgs& r, ScatterArgs s, BucketArgs b, int grid, hipStream_t st) {
+    // the rank and scatter passes: the same blocks over the same tiles (a block's rows of a bucket
+    // fill exactly its positions)
+    const int blocks = grid > 0 && grid < kBucketBlocks ? grid : kBucketBlocks;
+    const dim3 g(blocks), blk(256);
     if (r.nbuckets > kBucketMax || b.gpb != (1u << r.gshift)) return hipErrorInvalidValue;
+    if (blocks < kBucketBlocks) {  // k_group_scan reads kBucketBlocks counts per bucket: the absent blocks' are 0
+        const hipError_t e = hipMemsetAsync(r.bh, 0, (size_t)r.nbuckets * kBucketBlocks * sizeof(unsigned), st);
+        if (e != hipSuccess) return e;
+    }
+    const bool strided = r.m > (long long)blocks * kScatterTile;
     bool fixed = true;
     for (int p = 0; p < r.nkeys && p < kMaxKeys; ++p) fixed = fixed && r.k[p].type != kTypeUtf8;
     switch (r.nkeys * 2 + (fixed ? 1 : 0)) {
@@ -1330,8 +1347,10 @@ hipError_t launch_buckets(const RankArgs& r, ScatterArgs s, BucketArgs b, hipStr
         case 9: hipLaunchKernelGGL(k_group_rank_fixed<4>, g, blk, 0, st, r); break;
         default: return hipErrorInvalidValue;
     }
+    if (strided) count_strided_launch();
     hipLaunchKernelGGL(k_group_scan, dim3(r.nbuckets), dim3(kBucketBlocks), 0, st, r.bh, (unsigned*)s.tot);
     hipLaunchKernelGGL(k_group_scatter, g, blk, 0, st, s);
+    if (strided) count_strided_launch();
     const size_t lds = (size_t)b.gpb * (size_t)b.words * 8;
     if (lds > (size_t)kBucketRecordLdsBig || b.nbuckets > kBucketMax || b.splits < 1) return hipErrorInvalidValue;
     if (lds > (size_t)kBucketRecordLds) {  // more than 64 KiB per workgroup: raise the kernel's limit (once)
@@ -1345,31 +1364,31 @@ hipError_t launch_buckets(const RankArgs& r, ScatterArgs s, BucketArgs b, hipStr
 }
 
 hipError_t launch_emit(EmitArgs a, u64* sk, u64* sk2, unsigned* sv, unsigned* sv2, unsigned* null_at, void* tmp,
-                       size_t* tmp_bytes, hipStream_t st) {
+                       size_t* tmp_bytes, int grid, hipStream_t st) {
     if (!tmp) return rocprim::radix_sort_pairs(nullptr, *tmp_bytes, sk, sk2, sv, sv2, a.ngroups, 0, 64, st);
     const u64 ng = a.ngroups;
     hipError_t e = hipMemsetAsync(null_at, 0xff, 8, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_group_sortkey, dim3(grid_for((long long)ng)), dim3(256), 0, st, a.ktype, ng, a.knull, a.kw, sk,
-                       sv, null_at);
+    hipLaunchKernelGGL(k_group_sortkey, dim3(grid_for((long long)ng, grid)), dim3(256), 0, st, a.ktype, ng, a.knull, a.kw,
+                       sk, sv, null_at);
     e = rocprim::radix_sort_pairs(tmp, *tmp_bytes, sk, sk2, sv, sv2, ng, 0, 64, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_group_nullpos, dim3(grid_for((long long)ng)), dim3(256), 0, st, (const unsigned*)sv2, ng,
+    hipLaunchKernelGGL(k_group_nullpos, dim3(grid_for((long long)ng, grid)), dim3(256), 0, st, (const unsigned*)sv2, ng,
                        null_at);
     a.order = sv2;
     a.null_at = null_at;
-    hipLaunchKernelGGL(k_group_emit, dim3(grid_for((long long)ng)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_group_emit, dim3(grid_for((long long)ng, grid)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
-hipError_t launch_round(const RoundArgs& a, hipStream_t st) {
+hipError_t launch_round(const RoundArgs& a, int grid, hipStream_t st) {
     if (!a.ngroups || !a.naggs) return hipSuccess;
-    hipLaunchKernelGGL(k_group_round, dim3(grid_for((long long)(a.ngroups * a.naggs), kRoundBlock)),
+    hipLaunchKernelGGL(k_group_round, dim3(grid_for((long long)(a.ngroups * a.naggs), grid, kRoundBlock)),
                        dim3(kRoundBlock), 0, st, a);
     return hipGetLastError();
 }
 
-hipError_t launch_normalize(u64* acc, int words, const int* foff, int nf, u64 ngroups, hipStream_t st) {
+hipError_t launch_normalize(u64* acc, int words, const int* foff, int nf, u64 ngroups, int grid, hipStream_t st) {
     if (!nf || !ngroups) return hipSuccess;
     NormArgs a{};
     a.acc = acc;
@@ -1377,7 +1396,7 @@ hipError_t launch_normalize(u64* acc, int words, const int* foff, int nf, u64 ng
     a.nf = nf;
     for (int f = 0; f < nf && f < kMaxAggs; ++f) a.foff[f] = foff[f];
     a.ngroups = ngroups;
-    hipLaunchKernelGGL(k_group_normalize, dim3(grid_for((long long)(ngroups * nf))), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_group_normalize, dim3(grid_for((long long)(ngroups * nf), grid)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

@@ -74,14 +74,14 @@ struct Args {
     Hdr* hdr;
 };
 
-// launches on `stream` (asynchronous)
+// launches on `stream` (asynchronous); grid: groupby.h "Diagnostic grid cap" (0: the launch's own cap)
 hipError_t launch_init(unsigned long long* pref, unsigned* best, Ent* ent, int is_min, unsigned long long g0,
-                       unsigned long long g1, hipStream_t stream);
-hipError_t launch_find(const Args& a, hipStream_t stream);  // prefix, candidates, measure (adds to Hdr::need)
-hipError_t launch_keep(const Args& a, hipStream_t stream);
+                       unsigned long long g1, int grid, hipStream_t stream);
+hipError_t launch_find(const Args& a, int grid, hipStream_t stream);  // prefix, candidates, measure (adds to Hdr::need)
+hipError_t launch_keep(const Args& a, int grid, hipStream_t stream);
 // every live string of `ent` copied from `from` into `to` (reserving at to_hdr), ent[g].off updated
 hipError_t launch_compact(Ent* ent, unsigned long long ngroups, const unsigned char* from, unsigned char* to,
-                          unsigned long long to_cap, Hdr* to_hdr, hipStream_t stream);
+                          unsigned long long to_cap, Hdr* to_hdr, int grid, hipStream_t stream);
 
 }  // namespace sx
 }  // namespace dfmi

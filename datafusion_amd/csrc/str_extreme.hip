@@ -6,6 +6,7 @@
 // least value.
 #include <hip/hip_runtime.h>
 
+#include "groupby.h"
 #include "str_extreme.h"
 
 namespace dfmi {
@@ -169,37 +170,45 @@ __global__ __launch_bounds__(256) void k_sx_compact(Ent* ent, u64 ngroups, const
     }
 }
 
-static int grid_for(long long items, int cap = 1024) {
+// Workgroups for `items`, at most `cap` -- at most `diag` when that is set
+// (DFMI_GROUP_GRID, groupby.h "Diagnostic grid cap"); a launch that needs more
+// than one trip of its grid counts itself.
+static int grid_for(long long items, int diag, int cap = 1024) {
+    if (diag > 0 && diag < cap) cap = diag;
     const long long g = (items + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+    const int blocks = (int)(g < 1 ? 1 : (g > cap ? cap : g));
+    if (items > (long long)blocks * 256) gb::count_strided_launch();
+    return blocks;
 }
 
-hipError_t launch_init(u64* pref, unsigned* best, Ent* ent, int is_min, u64 g0, u64 g1, hipStream_t st) {
+hipError_t launch_init(u64* pref, unsigned* best, Ent* ent, int is_min, u64 g0, u64 g1, int grid, hipStream_t st) {
     if (g1 <= g0) return hipSuccess;
-    hipLaunchKernelGGL(k_sx_init, dim3(grid_for((long long)(g1 - g0))), dim3(256), 0, st, pref, best, ent, is_min, g0, g1);
+    hipLaunchKernelGGL(k_sx_init, dim3(grid_for((long long)(g1 - g0), grid)), dim3(256), 0, st, pref, best, ent, is_min, g0,
+                       g1);
     return hipGetLastError();
 }
 
-hipError_t launch_find(const Args& a, hipStream_t st) {
+hipError_t launch_find(const Args& a, int grid, hipStream_t st) {
     if (a.m <= 0 || !a.ngroups) return hipSuccess;
     // one group: a few thousand atomics on its one word per batch (one per wave of a capped grid)
-    if (!a.rg) hipLaunchKernelGGL(k_sx_prefix_one, dim3(grid_for(a.m, 512)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_sx_prefix, dim3(grid_for(a.m)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_sx_candidates, dim3(grid_for(a.m)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_sx_measure, dim3(grid_for((long long)a.ngroups)), dim3(256), 0, st, a);
+    if (!a.rg) hipLaunchKernelGGL(k_sx_prefix_one, dim3(grid_for(a.m, grid, 512)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_sx_prefix, dim3(grid_for(a.m, grid)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_sx_candidates, dim3(grid_for(a.m, grid)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_sx_measure, dim3(grid_for((long long)a.ngroups, grid)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
-hipError_t launch_keep(const Args& a, hipStream_t st) {
+hipError_t launch_keep(const Args& a, int grid, hipStream_t st) {
     if (a.m <= 0 || !a.ngroups) return hipSuccess;
-    hipLaunchKernelGGL(k_sx_keep, dim3(grid_for((long long)a.ngroups)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_sx_keep, dim3(grid_for((long long)a.ngroups, grid)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
-hipError_t launch_compact(Ent* ent, u64 ngroups, const u8* from, u8* to, u64 to_cap, Hdr* to_hdr, hipStream_t st) {
+hipError_t launch_compact(Ent* ent, u64 ngroups, const u8* from, u8* to, u64 to_cap, Hdr* to_hdr, int grid,
+                          hipStream_t st) {
     if (!ngroups) return hipSuccess;
-    hipLaunchKernelGGL(k_sx_compact, dim3(grid_for((long long)ngroups)), dim3(256), 0, st, ent, ngroups, from, to, to_cap,
-                       to_hdr);
+    hipLaunchKernelGGL(k_sx_compact, dim3(grid_for((long long)ngroups, grid)), dim3(256), 0, st, ent, ngroups, from, to,
+                       to_cap, to_hdr);
     return hipGetLastError();
 }
 

@@ -35,12 +35,15 @@ def _vals(vs):
     return [(v.type, v.is_null, v.count, 0 if v.is_null else v.bits) for v in vs]
 
 
-def run_multi(schema, batch, pred, keys, aggs, flags=FL, batch_rows=0):
+def run_multi(schema, batch, pred, keys, aggs, flags=FL, batch_rows=0, ref=None):
     """Device groups of GROUP BY keys against the oracle's: keys (all parts),
-    Utf8 key bytes, row counts and values bit for bit; or the same error."""
-    ref = ref_err = dev = dev_err = None
+    Utf8 key bytes, row counts and values bit for bit; or the same error.
+    ref: the oracle's groups of this very query, evaluated once by the caller
+    and shared between device runs."""
+    ref_err = dev = dev_err = None
     try:
-        ref = oracle_aggregate_grouped_multi(schema, batch, pred, keys, aggs, flags, batch_rows)
+        if ref is None:
+            ref = oracle_aggregate_grouped_multi(schema, batch, pred, keys, aggs, flags, batch_rows)
     except ExecutionError as e:
         ref_err = e
     st = None

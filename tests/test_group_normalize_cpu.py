@@ -151,5 +151,19 @@ def test_trip_counter_is_exported_and_starts_at_zero():
 def test_design_names_the_knob_and_the_counter():
     import os
     text = open(os.path.join(ROOT, "DESIGN.md"), encoding="utf-8").read()
-    for word in ("DFMI_GROUP_NORM_ROWS", "dfmi_internal_group_normalize_trips", "dfmi_internal_group_records"):
+    for word in ("DFMI_GROUP_NORM_ROWS", "dfmi_internal_group_normalize_trips", "dfmi_internal_group_records",
+                 "DFMI_GROUP_GRID", "dfmi_internal_group_strided_launches", "test_gpu_groupby_stride.py"):
         assert word in text, word
+
+
+def test_strided_launch_counter_is_exported_and_starts_at_zero():
+    """dfmi_internal_group_strided_launches (groupby.h "Diagnostic grid cap"): exported by the built library and 0
+    in a fresh process, with or without the grid knob in its environment -- nothing counts before a launch."""
+    import os
+    code = ("import ctypes as C; L = C.CDLL(%r); f = L.dfmi_internal_group_strided_launches; f.restype = C.c_long; "
+            "print(f())" % _abi.LIB_PATH)
+    for knobs in ({}, {"DFMI_DIAG": "1", "DFMI_GROUP_GRID": "3"}):
+        out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120,
+                             env=dict(os.environ, **knobs))
+        assert out.returncode == 0, out.stderr
+        assert out.stdout.strip() == "0"
